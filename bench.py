@@ -11,9 +11,13 @@ Weights are synthetic (no checkpoint ships with the reference), broadcast once f
 over RCCL; streams are independent, so N GPUs = N streams, no data-path collective
 ("scaling": "weak").
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: the fp32-MFMA implicit-GEMM
-convolution, per-launch time from HIP events on the launching stream) and `cpu_baseline`
-(the CPU oracle restatement of the same frame, timed on this box's host cores).
+Prints ONE JSON line (rank 0).  A plain run times exactly --steps frames after --warmup and
+reports the headline only.  `--full` adds the measurements beyond the headline: `roofline`
+(dominant kernel: the fp32-MFMA implicit-GEMM convolution, per-launch time from HIP events on
+the launching stream), the GroupDW bandwidth and PCIe-inclusive loop, the configs[2] / [4] /
+split-fp16 / lock-step / 271 extras and `cpu_baseline` (the CPU oracle restatement of the same
+frame, timed on this box's host cores).  `--dump-outputs DIR` writes what the last timed step
+returned as DIR/<name>.npy (float32 / float64), for comparing two builds output for output.
 """
 import argparse
 import json
@@ -96,22 +100,56 @@ class Confidences:
 
 
 def run_frames(sess, crops, p, conf, n):
+    """`n` frames of one video; returns the last frame's result block (float64[8], Session.collect), None when n = 0."""
+    out = None
     for i in range(n):
         picks = select_memory(conf.view(), p.mem_queue_size)
         out = sess.frame(crops[i % crops.shape[0]], picks, (63.5, 63.5), inplace=True)     # resident crops, read where they lie
         conf.append(float(out[1]))
+    return out
 
 
 def run_frames_multi(group, n):
     """`group`: [(session, crops, p, conf, stream)] — S independent videos on one GPU, each on its
     own HIP stream: submit a frame for every stream, then collect them (frames of different
-    videos overlap on the GPU; each video stays sequential)."""
+    videos overlap on the GPU; each video stays sequential).  Returns the last frame's result block of every video."""
+    outs = None
     for i in range(n):
         for sess, crops, p, conf, st in group:
             with torch.cuda.stream(st):
                 sess.submit(crops[i % crops.shape[0]], select_memory(conf.view(), p.mem_queue_size), (63.5, 63.5), inplace=True)
+        outs = []
         for sess, crops, p, conf, st in group:
-            conf.append(float(sess.collect()[1]))
+            outs.append(sess.collect())
+            conf.append(float(outs[-1][1]))
+    return outs
+
+
+DUMP_LIMIT = 1 << 22        # --dump-outputs: an output of more elements is written as a fixed sample of DUMP_SAMPLE of them
+DUMP_SAMPLE = 1 << 20
+
+
+def write_outputs(path, arrays):
+    """`--dump-outputs`: every array as `path`/<name>.npy, float64 when it is float64, float32 otherwise.  An array of more than
+    DUMP_LIMIT elements is written as its values at DUMP_SAMPLE flat positions drawn with seed 0 (sorted, with repeats): the same
+    positions on every run, so two builds compare element for element."""
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        v = torch.as_tensor(v).detach()
+        if v.numel() > DUMP_LIMIT:
+            idx = np.sort(np.random.default_rng(0).integers(0, v.numel(), DUMP_SAMPLE))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        v = v.cpu().double() if v.dtype == torch.float64 else v.cpu().float()
+        np.save(os.path.join(path, name + '.npy'), v.numpy())
+
+
+def session_outputs(group, outs):
+    """What a caller of the headline loop holds after its last step, one row per video: the result block of that frame
+    (float64[8] = argmax, score, penalty, x1, y1, x2, y2, pscore), the memory feature that frame pooled (PrRoIPool of the winning
+    box, [256, 7, 7]) and the confidence of every frame so far (the list select_memory picks from)."""
+    return {'result': np.stack(outs),
+            'memory_feature': torch.cat([sess.memory_feature(sess.n - 1) for sess, *_ in group]),
+            'confidences': np.stack([conf.view() for _, _, _, conf, _ in group])}
 
 
 K_PWPAIR, K_PW1, K_SC3, K_PW3 = 18, 19, 20, 21          # plan op kinds of the fused pointwise pair / the streaming 1x1 and 3x3 convs (csrc/plan.hip)
@@ -444,16 +482,18 @@ def _timed(run, min_seconds, steps=0):
     return n, time.perf_counter() - t0
 
 
-def measure_backbone_bf16(model, device, batch=64, size=255, steps=0, warmup=2, min_seconds=1.0, top=5):
+def measure_backbone_bf16(model, device, batch=64, size=255, steps=0, warmup=2, min_seconds=1.0, top=5, dump=None):
     """BASELINE configs[2]: batch-64 bf16 backbone (+neck) on v_mfma_f32_16x16x32_bf16, the MFMA-roofline
     run.  Whole-graph replay for crops/s; per-conv HIP-event times (plan.profile, each op once per
-    pass in graph order) for TFLOP/s over the convolutions."""
+    pass in graph order) for TFLOP/s over the convolutions.  `dump`: --dump-outputs directory."""
     e = model.engine
     x = torch.from_numpy(synth.crop(3000, batch, size)).to(device)
     for _ in range(max(2, warmup)):
         e.features_bf16(x)
     p = next(v for k, v in e._feat.items() if k[:3] == ('bf16', batch, size))
     n, dt = _timed(p['plan'].run, min_seconds, steps)
+    if dump:
+        write_outputs(dump, {'features': p['xf'].permute(0, 3, 1, 2)})      # what features_bf16 returns: the neck map, NCHW
     prof = stable_profile(p['plan'], dt / n * 1e3)
     convs = iter(p['log'])
     ms_conv = fl_conv = ms_all = 0.0
@@ -534,7 +574,7 @@ def stable_profile(plan, step_ms, frames=3, tries=4):
 def backbone_bf16(a, device):
     """`--workload backbone_bf16`: configs[2] as its own JSON line."""
     model, _ = build_model(0, 1, device)
-    r = measure_backbone_bf16(model, device, a.batch, a.size, a.steps, a.warmup, a.min_seconds)
+    r = measure_backbone_bf16(model, device, a.batch, a.size, a.steps, a.warmup, a.min_seconds, dump=a.dump_outputs)
     line = {
         'metric': 'backbone crops/s (255x255, ResNet-50 layer3 + neck, bf16, batch %d)' % a.batch,
         'value': r['value'], 'unit': 'crops/s', 'n_gpus': 1, 'steps': r['steps'], 'warmup': a.warmup,
@@ -700,6 +740,9 @@ def track_mixed(a, rank, world, device):
     streams.barrier()
     dt = streams.max_over_ranks(time.perf_counter() - t0, device=device)
     if rank == 0:
+        if a.dump_outputs:      # what engine.track_mixed returns: cls, bbox, cls_mem, the neck map (NHWC buffer, returned as NCHW)
+            write_outputs(a.dump_outputs, {'cls': p['cls2'][0], 'bbox': p['bbox'], 'cls_mem': p['cls2'][1],
+                                           'features': p['xf'].permute(0, 3, 1, 2)})
         print(json.dumps({
             'metric': 'tracker FPS (255x255 search, ResNet-50), %s backbone%s + fp32 xcorr, batch %d per GPU'
                       % (a.lp, '' if a.heads_f32 else ' and head convs', b),
@@ -779,16 +822,59 @@ def plumbing_only(a):
     streams.barrier()
 
 
+def full_measurements(line, a, model, sess, device, world):
+    """`--full`: everything the line carries beyond the headline, each sub-measurement under its own key of `line` (rank 0, after
+    the timed steps and the output dump: the roofline profile replays the headline session's frames)."""
+    line['roofline'] = roofline(sess, frames=10)
+
+    def extra(key, fn):
+        # a sub-measurement that fails must not take the headline line with it: the line then carries the error text under its key
+        try:
+            line[key] = fn()
+        except Exception as exc:      # noqa: BLE001
+            line[key] = {'error': '%s: %s' % (type(exc).__name__, str(exc)[:300])}
+
+    def mixed_b32():
+        pm = measure_track_mixed(model, device, 32, a.size)
+        n, t = _timed(pm['plan'].run, 1.0)
+        return {'workload': 'configs[4], one GPU: fp16 backbone + head convs, fp32 xcorr / reduce / predictions, 32 streams in '
+                            'lock step, N_q=7, one hipGraph', 'value': round(32 * n / t, 1), 'unit': 'frames/s',
+                'steps': n, 'ms_per_step': round(t / n * 1e3, 3), 'dtype': 'fp16+f32',
+                'roofline': mixed_roofline(pm, 32, a.size, n, t)}
+    if not a.no_xcorr:
+        extra('xcorr_hbm', lambda: xcorr_bandwidth(device))
+    if world == 1:
+        extra('video_loop_pcie_inclusive', lambda: video_loop(model, device))
+    if world == 1 and not a.no_extras:
+        # the two low-precision north-star configurations, the opt-in split-fp16 frame and the fp32 lock-step mode, measured by
+        # the same process (each a few seconds; their own full lines: --workload backbone_bf16 / track_mixed)
+        extra('backbone_bf16_b64', lambda: measure_backbone_bf16(model, device, 64, a.size))
+        extra('track_mixed_b32', mixed_b32)
+        extra('track_split16', lambda: measure_track_split16(model, device, a.size))
+        extra('lockstep_f32_b4', lambda: measure_lockstep_f32(model, device, 4, a.size))
+        if a.size != 271:
+            extra('track_271', lambda: measure_track_271(model, device))
+    if world == 1 and not a.no_cpu_baseline:
+        extra('cpu_baseline', cpu_baseline)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=300)
     ap.add_argument('--warmup', type=int, default=30)
     ap.add_argument('--size', type=int, default=255)
-    ap.add_argument('--min-seconds', type=float, default=2.0,
-                    help='the timed region lasts at least this long: steps = max(--steps, ceil(min_seconds / step time)); 0 = exactly --steps')
+    ap.add_argument('--min-seconds', type=float, default=0.0,
+                    help='the timed region lasts at least this long: steps = max(--steps, ceil(min_seconds / step time)); 0 (the default) = '
+                         'exactly --steps')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline (roofline profile, GroupDW bandwidth, PCIe-inclusive loop, the '
+                         'configs[2]/[4]/split-fp16/lock-step/271 extras, CPU baseline); a plain run sets up, warms up, times --steps and prints')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps write what the last one returned as DIR/<name>.npy (float32 / float64; an output of more '
+                         'than %d elements as a fixed seeded sample of %d)' % (DUMP_LIMIT, DUMP_SAMPLE))
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the configs[2]/[4]/lock-step sub-objects of the default line')
+    ap.add_argument('--no-extras', action='store_true', help='skip the configs[2]/[4]/lock-step sub-objects of the --full line')
     ap.add_argument('--no-xcorr', action='store_true')
     ap.add_argument('--workload', default='track', choices=['track', 'backbone_bf16', 'track_mixed'])
     ap.add_argument('--lp', default='fp16', choices=['fp16', 'bf16'])
@@ -804,6 +890,8 @@ def main():
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         self_launch(a)
     if a.plumbing_only:
+        if a.dump_outputs:
+            raise SystemExit('--dump-outputs: --plumbing-only runs no frames')
         return plumbing_only(a)
     if not torch.cuda.is_available():
         raise SystemExit('bench.py needs an MI355X (no CPU fallback for the HIP path)')
@@ -842,12 +930,14 @@ def main():
     streams.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    go(steps)
+    outs = go(steps)
     torch.cuda.synchronize()
     streams.barrier()
     dt = streams.max_over_ranks(time.perf_counter() - t0, device=device)
 
     if rank == 0:
+        if a.dump_outputs:
+            write_outputs(a.dump_outputs, session_outputs(group, [outs] if S == 1 else outs))
         fps = world * S * steps / dt
         line = {
             'metric': 'tracker FPS (255x255 search, ResNet-50)', 'value': round(fps, 2), 'unit': 'frames/s',
@@ -855,7 +945,7 @@ def main():
             'ms_per_step': round(dt / steps * 1e3, 4),
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
             # the engine's default: exact fp32 products (v_mfma_f32_16x16x4_f32), fp32 storage and accumulation - the reference's
-            # arithmetic; the opt-in split-fp16 mode is timed as the labelled extra `track_split16` below
+            # arithmetic; the opt-in split-fp16 mode is timed as the labelled extra `track_split16` of --full
             'dtype': f32_dtype_label(model.engine),
             'data': 'synthetic',
             'config': {'workload': 'configs[1]: batch=1 ResNet-50(layer3)+neck, fused depthwise xcorr, cls/reg/'
@@ -867,37 +957,8 @@ def main():
                        # distinct pinned result blocks and distinct HIP streams: every video has its own
                        'result_streams': len({g[0].out8.data_ptr() for g in group}), 'hip_streams': len({g[4].cuda_stream for g in group})},
         }
-        line['roofline'] = roofline(sess, frames=10)
-
-        def extra(key, fn):
-            # a sub-measurement that fails must not take the headline line with it: the line then carries the error text under its key
-            try:
-                line[key] = fn()
-            except Exception as exc:      # noqa: BLE001
-                line[key] = {'error': '%s: %s' % (type(exc).__name__, str(exc)[:300])}
-
-        def mixed_b32():
-            pm = measure_track_mixed(model, device, 32, a.size)
-            n, t = _timed(pm['plan'].run, 1.0)
-            return {'workload': 'configs[4], one GPU: fp16 backbone + head convs, fp32 xcorr / reduce / predictions, 32 streams in '
-                                'lock step, N_q=7, one hipGraph', 'value': round(32 * n / t, 1), 'unit': 'frames/s',
-                    'steps': n, 'ms_per_step': round(t / n * 1e3, 3), 'dtype': 'fp16+f32',
-                    'roofline': mixed_roofline(pm, 32, a.size, n, t)}
-        if not a.no_xcorr:
-            extra('xcorr_hbm', lambda: xcorr_bandwidth(device))
-        if world == 1:
-            extra('video_loop_pcie_inclusive', lambda: video_loop(model, device))
-        if world == 1 and not a.no_extras:
-            # the two low-precision north-star configurations, the opt-in split-fp16 frame and the fp32 lock-step mode, measured by
-            # the same process (each a few seconds; their own full lines: --workload backbone_bf16 / track_mixed)
-            extra('backbone_bf16_b64', lambda: measure_backbone_bf16(model, device, 64, a.size))
-            extra('track_mixed_b32', mixed_b32)
-            extra('track_split16', lambda: measure_track_split16(model, device, a.size))
-            extra('lockstep_f32_b4', lambda: measure_lockstep_f32(model, device, 4, a.size))
-            if a.size != 271:
-                extra('track_271', lambda: measure_track_271(model, device))
-        if world == 1 and not a.no_cpu_baseline:
-            extra('cpu_baseline', cpu_baseline)
+        if a.full:
+            full_measurements(line, a, model, sess, device, world)
         line['build_info'] = build_info_line()
         print(json.dumps(line))
     streams.barrier()

@@ -6,7 +6,7 @@ import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden')); sys.path.insert(0, os.path.join(ROOT, 'oracle'))
 import numpy as np, torch
-import sampling
+import golden_parts, sampling
 from usot_amd import synth, engine
 from usot_amd.model import USOT
 from usot_amd import hip
@@ -16,7 +16,7 @@ if os.environ.get('USOT_SLICED'):            # channel-sliced pairs on (layer2 s
     engine.OPTIONS['fused_f32_sliced'] = True
 if os.environ.get('USOT_NO_SLICE'):          # fused pairs without the channel-sliced form
     hip.pw_pair_f32_ws = lambda *a, **k: None
-gold = dict(np.load(os.path.join(ROOT, 'tests', 'golden', 'golden_model.npz')))
+gold = golden_parts.load(os.path.join(ROOT, 'tests', 'golden', 'golden_model.npz'))
 errs = []
 def check(name, arr):
     a = np.asarray(arr, dtype=np.float32)

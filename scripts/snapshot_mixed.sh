@@ -16,5 +16,5 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 python scripts/pmc_lp_traffic.py "$(db "$out/pmc_mx_FETCH_SIZE")" "$(db "$out/pmc_mx_WRITE_SIZE")" "$out/pmc_traffic_mixed.json" "$commit" stem_pool_lp "bench.py $mx" > /dev/null
 rm -rf "$out/prof_mx" "$out/pmc_mx_FETCH_SIZE" "$out/pmc_mx_WRITE_SIZE"
-timeout 300 python bench.py --workload track_mixed --batch 32 > "$out/config5_fp16_mixed_b32_bench.json" 2>> "$out/bench.err"
+timeout 300 python bench.py --workload track_mixed --batch 32 --min-seconds 2 > "$out/config5_fp16_mixed_b32_bench.json" 2>> "$out/bench.err"
 head -c 600 "$out/config5_fp16_mixed_b32_bench.json"; echo; head -8 "$out/config5_kernel_stats.txt"

@@ -54,8 +54,8 @@ def pytest_collection_modifyitems(config, items):
 
 @pytest.fixture(scope='session')
 def gold_model():
-    with np.load(os.path.join(GOLD, 'golden_model.npz')) as z:
-        return {k: z[k] for k in z.files}
+    import golden_parts
+    return golden_parts.load(os.path.join(GOLD, 'golden_model.npz'))
 
 
 @pytest.fixture(scope='session')

@@ -12,6 +12,7 @@ import os
 
 import numpy as np
 
+import golden_parts
 from sampling import sample_index
 
 GOLD = os.path.dirname(os.path.abspath(__file__))
@@ -21,8 +22,7 @@ FLOOR = 2e-7
 
 
 def load():
-    with np.load(os.path.join(GOLD, 'golden_model_f64.npz')) as z:
-        return {k: z[k] for k in z.files}
+    return golden_parts.load(os.path.join(GOLD, 'golden_model_f64.npz'))
 
 
 def run_model(net, dev='cuda:0'):

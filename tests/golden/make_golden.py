@@ -52,6 +52,7 @@ sys.path.insert(1, REPO)
 sys.path.insert(2, GOLD)
 from usot_amd import synth  # noqa: E402
 from sampling import summarize  # noqa: E402
+import golden_parts  # noqa: E402
 
 assert ref_models.__file__.startswith(REF), ref_models.__file__
 torch.manual_seed(0)
@@ -159,9 +160,8 @@ def do_model():
             ka = gx.standard_normal((2, 24, hk, wk)).astype(np.float32)
             g['xcorr%d/x' % i], g['xcorr%d/k' % i] = xa, ka
             g['xcorr%d/out' % i] = xcorr_depthwise(t(xa), t(ka)).numpy()
-    np.savez_compressed(os.path.join(GOLD, 'golden_model.npz'), **g)
-    print('model goldens: %d arrays, %.1f KB' % (
-        len(g), os.path.getsize(os.path.join(GOLD, 'golden_model.npz')) / 1024))
+    files = golden_parts.save(os.path.join(GOLD, 'golden_model.npz'), g)
+    print('model goldens: %d arrays, %.1f KB in %d parts' % (len(g), sum(os.path.getsize(f) for f in files) / 1024, len(files)))
 
 
 def _import_ref_tracker(resize=None):
@@ -572,11 +572,10 @@ def do_model64():
             out['track_mem_b2/' + nm] = ten.numpy()
         return out
     path = os.path.join(GOLD, 'golden_model_f64.npz')
-    if os.path.exists(path) and os.environ.get('USOT_GOLDEN_REGEN') != '1':
+    if golden_parts.parts(path) and os.environ.get('USOT_GOLDEN_REGEN') != '1':
         # families already in the fixture are kept as committed (only missing ones are computed): adding the third family
         # in round 4 must not touch the entries rounds 2-3 were gated on
-        with np.load(path) as z:
-            g.update({k: z[k] for k in z.files})
+        g.update(golden_parts.load(path))
     for fam in synth.FAMILIES:
         if any(k.startswith(fam + '/') for k in g):
             print('%s: kept (%d arrays)' % (fam, sum(k.startswith(fam + '/') for k in g)))
@@ -591,8 +590,8 @@ def do_model64():
             o64 = run(net.double(), lambda a: a.double())
         for k in o32:
             put(fam, k, o32[k], o64[k])
-    np.savez_compressed(path, **g)
-    print('float64 goldens: %d arrays, %.1f KB' % (len(g), os.path.getsize(os.path.join(GOLD, 'golden_model_f64.npz')) / 1024))
+    files = golden_parts.save(path, g)
+    print('float64 goldens: %d arrays, %.1f KB in %d parts' % (len(g), sum(os.path.getsize(f) for f in files) / 1024, len(files)))
 
 
 def do_datasets():

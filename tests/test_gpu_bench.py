@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -31,7 +32,7 @@ def _bench(*args, timeout=600):
 
 
 def test_bench_two_ranks_shard_streams_and_broadcast_weights():
-    j = _bench('--gpus', '2', '--steps', '50', '--warmup', '5', '--min-seconds', '0', '--no-extras', '--no-xcorr', '--no-cpu-baseline')
+    j = _bench('--gpus', '2', '--steps', '50', '--warmup', '5', '--min-seconds', '0', '--full', '--no-extras', '--no-xcorr', '--no-cpu-baseline')
     assert j['n_gpus'] == 2 and j['steps'] == 50 and j['warmup'] == 5 and j['scaling'] == 'weak'
     assert j['config']['streams'] == 2 and j['config']['streams_per_gpu'] == 1
     assert 'broadcast %d B in ' % WEIGHT_BYTES in j['config']['weights'] and 'backend gloo, 2 ranks' in j['config']['weights'], j['config']['weights']
@@ -46,7 +47,7 @@ def test_bench_two_ranks_shard_streams_and_broadcast_weights():
 def test_bench_line_carries_the_contract_fields():
     """One rank, the short form of the driver's command: every key the contract names, the roofline object with its
     algorithmic bytes beside the measured traffic, and the 271 x 271 sub-object."""
-    j = _bench('--steps', '40', '--warmup', '5', '--min-seconds', '0', '--no-xcorr', '--no-cpu-baseline')
+    j = _bench('--steps', '40', '--warmup', '5', '--min-seconds', '0', '--full', '--no-xcorr', '--no-cpu-baseline')
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
               'dtype', 'data', 'config', 'roofline'):
         assert k in j, k
@@ -88,3 +89,28 @@ def test_eight_videos_on_one_gpu_are_eight_sessions_and_beat_one_stream():
     assert eight['value'] >= 1.2 * one['value'], (eight['value'], one['value'])
     # value counts the frames of ALL videos: steps x 8 / time
     assert abs(eight['value'] - 8 * 1e3 / eight['ms_per_step']) <= 0.01 * eight['value']
+
+
+def test_plain_run_times_exactly_the_requested_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full): exactly --steps timed frames, the headline fields and nothing measured beside them; --dump-outputs
+    writes what the last timed step returned, and a second run with the same arguments (same seeded inputs) writes the same."""
+    runs = []
+    for k in range(2):
+        d = tmp_path / ('run%d' % k)
+        j = _bench('--steps', '25', '--warmup', '3', '--dump-outputs', str(d))
+        assert j['steps'] == 25 and j['steps_requested'] == 25 and j['warmup'] == 3 and j['n_gpus'] == 1
+        assert j['unit'] == 'frames/s' and j['higher_is_better'] is True and j['dtype'] == 'f32'
+        assert abs(j['value'] - 1e3 / j['ms_per_step']) <= 0.01 * j['value']
+        for key in ('roofline', 'xcorr_hbm', 'video_loop_pcie_inclusive', 'backbone_bf16_b64', 'track_mixed_b32', 'track_split16',
+                    'lockstep_f32_b4', 'track_271', 'cpu_baseline'):
+            assert key not in j, key
+        out = {f.name[:-4]: np.load(str(f)) for f in d.iterdir()}
+        assert sorted(out) == ['confidences', 'memory_feature', 'result']
+        assert out['result'].shape == (1, 8) and out['result'].dtype == np.float64
+        assert out['memory_feature'].shape == (1, 256, 7, 7) and out['memory_feature'].dtype == np.float32
+        assert out['confidences'].shape == (1, 1 + 3 + 25) and out['confidences'].dtype == np.float64
+        assert all(np.isfinite(v).all() for v in out.values()) and np.abs(out['memory_feature']).max() > 0
+        assert out['confidences'][0, -1] == out['result'][0, 1]            # the last step's score is the last confidence
+        runs.append(out)
+    for name, v in runs[0].items():
+        np.testing.assert_allclose(runs[1][name], v, rtol=1e-5, atol=1e-6, err_msg=name)
