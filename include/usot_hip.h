@@ -583,6 +583,46 @@ int usot_rows_append_gather_f32(void *stream, const float *const *fresh, float *
                                 const int32_t *row_len, const int32_t *idx_dev, int n_pick, int slot_pos);
 int usot_plan_add_rows_append_gather(void *plan, const float *const *fresh, float *const *bank, float *const *picked,
                                      const int32_t *row_len, const int32_t *idx_dev, int n_pick, int slot_pos);
+/* ---- lock-step multi-video tracking (csrc/multitrack.hip): B videos ("slots") of one instance size step together in one
+ * frame graph.  Each kernel is ONE launch per step whatever B.  The step's control block `ctl` (pinned, device-mapped host
+ * memory, or device memory) is a USOT_STEP_HDR_BYTES header - the step tag, a double, at offset 0 - followed by B
+ * usot_slot_rec records.  Every kernel fetches the words of its slot once per workgroup, and every word is read before the
+ * decode publishes the slot's tag, so the host may rewrite the block as soon as all B tags are seen.
+ * Memory banks: one tensor per bank kind, [B * cap, row]; slot b's row r is global row b * cap + r. */
+#define USOT_STEP_HDR_BYTES 64
+typedef struct usot_slot_rec {
+    double tsz[2];            /* target size x scale_z (decode)                                                      */
+    uint64_t im;              /* device address of the slot's HWC uint8 image; 0 = the crop is not written (the host   */
+                              /* wrote it, or the slot is inactive)                                                  */
+    int32_t H, W;             /* image size                                                                          */
+    int32_t x0, y0, win;      /* crop window: origin in image coordinates (may be negative) and edge                 */
+    int32_t fill[3];          /* padding colour, B G R                                                               */
+    int32_t append_row;       /* global bank row that receives the PREVIOUS step's pooled feature (a scratch row when */
+                              /* nothing is pending)                                                                 */
+    int32_t next_row;         /* global row this step's feature is appended to by the next step (host bookkeeping)   */
+    int32_t picks[32];        /* N_q global bank rows gathered for this step's memory kernels                        */
+} usot_slot_rec;              /* 192 bytes */
+/* decode of B slots (one workgroup each, S <= 32): maps cls / cls_mem [B][S][S], bbox [B][4][S][S]; window [S][S] shared.
+ * out: B rows of 16 doubles, row b = usot_decode_dev_f32's results [0..8) and the step tag at [8], stored after the results
+ * behind a system-scope fence.  roi_out: B rows of 5 floats, (b, pool_label_search(box)) - the batch index is the slot. */
+int usot_decode_batch_f32(void *stream, const float *cls, const float *cls_mem, const float *bbox, const double *window,
+                          double *out, int B, int S, int instance_size, int stride, float ratio, double penalty_k,
+                          double window_influence, const void *ctl, float *roi_out);
+int usot_plan_add_decode_batch(void *plan, const float *cls, const float *cls_mem, const float *bbox, const double *window,
+                               double *out, int B, int S, int instance_size, int stride, float ratio, double penalty_k,
+                               double window_influence, const void *ctl, float *roi_out);
+/* append + gather of B slots: fresh[k] [B][row_len[k]] (the previous step's pooled feature and its three encodings), bank[k]
+ * [B * cap][row_len[k]], picked[k - 1] [B * n_pick][row_len[k]] (k = 1..3).  Slot b: fresh row b -> bank row append_row;
+ * picks[j] -> picked row b * n_pick + j, a pick equal to append_row read from fresh row b.  n_pick <= 32.  bank_rows = B * cap:
+ * a row outside [0, bank_rows) is never touched (such an append is dropped, such a pick gathers zeros). */
+int usot_rows_append_gather_batch_f32(void *stream, const float *const *fresh, float *const *bank, float *const *picked,
+                                      const int32_t *row_len, const void *ctl, int B, int n_pick, int bank_rows);
+int usot_plan_add_rows_append_gather_batch(void *plan, const float *const *fresh, float *const *bank, float *const *picked,
+                                           const int32_t *row_len, const void *ctl, int B, int n_pick, int bank_rows);
+/* crop + resize of B slots into out [B][3][S][S]: slot b's window from its record, usot_crop_resize_u8_f32's arithmetic;
+ * a slot whose image address is 0 is left untouched. */
+int usot_crop_resize_batch_u8_f32(void *stream, const void *ctl, float *out, int B, int S);
+int usot_plan_add_crop_resize_batch(void *plan, const void *ctl, float *out, int B, int S);
 int usot_plan_add_rows_copy(void *plan, const float *src, const int32_t *idx_dev, float *dst,
                             int n_rows, int row_len, int scatter);
 int usot_plan_fork(void *plan, int lane);

@@ -6,8 +6,11 @@
 #include <stdio.h>
 #include "usot_hip.h"
 #include "common.h"
+#include "head_common.h"
 
 namespace {
+
+using namespace usot_head;
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -554,68 +557,14 @@ __global__ __launch_bounds__(256) void rows_append_gather_kernel(const RowsAG k,
 // ---- SiamFC crop on the device (lib/utils/track_utils.py:30-119): window extraction with
 // mean-colour padding, OpenCV-style fixed-point bilinear resize (the arithmetic restated in
 // usot_amd/hostutils.py::resize_bilinear_u8) and HWC uint8 -> CHW float32, one thread per
-// output pixel.  Replaces ~1 ms of numpy per frame with one small kernel.
-struct CropK {
-    const unsigned char *im;      // [H][W][3]
-    float *out;                   // [3][S][S]
-    int H, W, S, win;
-    int x0, y0;                   // window origin in image coordinates (may be negative)
-    int fill[3];
-};
-
-__device__ __forceinline__ void crop_axis(int d, int n_src, int n_dst, int &s0, int &s1, int &w0, int &w1)
-{
-    // OpenCV's own arithmetic (see hostutils._resize_axis): double scale = 1 / (dst / src), the source
-    // coordinate rounded to float BEFORE the floor, float fraction, round-half-even coefficients
-    const double scale = 1.0 / ((double)n_dst / (double)n_src);
-    float f = (float)(((double)d + 0.5) * scale - 0.5);
-    int s = (int)floorf(f);
-    f -= (float)s;
-    if (s < 0) { f = 0.0f; s = 0; }
-    if (s >= n_src - 1) { f = 0.0f; s = n_src - 1; }
-    w1 = (int)rintf(f * 2048.0f);
-    w0 = (int)rintf((1.0f - f) * 2048.0f);
-    s0 = s;
-    s1 = min(s + 1, n_src - 1);
-}
-
-__device__ __forceinline__ int crop_px(const CropK &p, int wx, int wy, int c)
-{
-    const int ix = p.x0 + wx, iy = p.y0 + wy;
-    if ((unsigned)ix >= (unsigned)p.W || (unsigned)iy >= (unsigned)p.H) return p.fill[c];
-    return p.im[((long)iy * p.W + ix) * 3 + c];
-}
-
+// output pixel.  Replaces ~1 ms of numpy per frame with one small kernel.  The per-pixel arithmetic
+// (CropK, crop_axis, crop_px, crop_resize_px) lives in head_common.h, shared with the lock-step batch.
 __global__ __launch_bounds__(256) void crop_resize_kernel(const CropK p)
 {
     const int idx = blockIdx.x * 256 + threadIdx.x;
     if (idx >= p.S * p.S) return;
     const int dy = idx / p.S, dx = idx - dy * p.S;
-    if (p.win == p.S) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) p.out[((long)c * p.S + dy) * p.S + dx] = (float)crop_px(p, dx, dy, c);
-        return;
-    }
-    if (p.win == 2 * p.S) {          // exact 2x downscale: cv2.resize switches INTER_LINEAR to INTER_AREA
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const int v = (crop_px(p, 2 * dx, 2 * dy, c) + crop_px(p, 2 * dx + 1, 2 * dy, c) +
-                           crop_px(p, 2 * dx, 2 * dy + 1, c) + crop_px(p, 2 * dx + 1, 2 * dy + 1, c) + 2) >> 2;
-            p.out[((long)c * p.S + dy) * p.S + dx] = (float)v;
-        }
-        return;
-    }
-    int xa, xb, wxa, wxb, ya, yb, wya, wyb;
-    crop_axis(dx, p.win, p.S, xa, xb, wxa, wxb);
-    crop_axis(dy, p.win, p.S, ya, yb, wya, wyb);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const long top = (long)crop_px(p, xa, ya, c) * wxa + (long)crop_px(p, xb, ya, c) * wxb;
-        const long bot = (long)crop_px(p, xa, yb, c) * wxa + (long)crop_px(p, xb, yb, c) * wxb;
-        long v = ((((long)wya * (top >> 4)) >> 16) + (((long)wyb * (bot >> 4)) >> 16) + 2) >> 2;
-        v = v < 0 ? 0 : (v > 255 ? 255 : v);
-        p.out[((long)c * p.S + dy) * p.S + dx] = (float)v;
-    }
+    crop_resize_px(p, dx, dy);
 }
 
 // ---- decode (usot_tracker.py:138-163): one workgroup, double precision like the numpy
@@ -625,21 +574,7 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const CropK p)
 // thread — which still holds its cell's box, score and penalty in registers — publishes the
 // results (round 6; before: 256 threads x 3 cells, an 8-step LDS tree, thread 0 recomputing the
 // winner's cell: 10.8 us per frame in the graph).  Same expressions, same order: bit-identical.
-struct DecCell {
-    double ps, x1, y1, x2, y2, pen;
-    float sc;
-    int i;
-};
-
-// np.argmax semantics (usot_tracker.py:163): first maximum, and a NaN counts as the maximum (the first NaN wins);
-// index 0x7fffffff = "no cell" loses to everything
-__device__ __forceinline__ bool dec_better(double ov, int oi, double mv, int mi)
-{
-    const bool on = ov != ov, mn = mv != mv;
-    return oi != 0x7fffffff &&
-        (mi == 0x7fffffff || (on && !mn) || (on == mn && (on ? oi < mi : (ov > mv || (ov == mv && oi < mi)))));
-}
-
+// DecCell and dec_better (np.argmax: first maximum, first NaN wins): head_common.h
 __global__ __launch_bounds__(1024) void decode_kernel(
     const float *__restrict__ cls, const float *__restrict__ cls_mem, const float *__restrict__ bbox,
     const double *__restrict__ window, double *__restrict__ out, int S, int instance_size, int stride,
@@ -1076,7 +1011,10 @@ extern "C" int usot_device_slot(void)
 
 extern "C" int usot_device_guard(void) { return usot_device_slot() >= 0 ? USOT_OK : USOT_ESTATE; }
 
-extern "C" int usot_abi_version(void) { return 6; }   // 2: usot_conv_desc.w_frag; 3: w_scale; 4: x_split / y_split; 5: ovf (conv + pw_pair descriptors), decode's out[9]; 6: usot_rows_append_gather_f32
+extern "C" int usot_abi_version(void) { return 6; }   // 2: usot_conv_desc.w_frag; 3: w_scale; 4: x_split / y_split; 5: ovf (conv + pw_pair descriptors), decode's out[9]; 6: usot_rows_append_gather_f32;
+// symbols added at 6 (no existing signature changed): the lock-step batch of csrc/multitrack.hip - usot_decode_batch_f32,
+// usot_rows_append_gather_batch_f32, usot_crop_resize_batch_u8_f32 and their plan adders (usot_plan_add_decode_batch,
+// usot_plan_add_rows_append_gather_batch, usot_plan_add_crop_resize_batch)
 
 extern "C" const char *usot_strerror(int code)
 {

@@ -24,7 +24,7 @@ extern "C" int usot_conv_resolve_tile(const usot_conv_desc *d);
 
 namespace {
 
-enum Kind { K_CONV, K_STEM, K_POOL, K_GDW, K_CONF, K_PRROI, K_PERM, K_DECODE, K_FORK, K_JOIN, K_ROWS, K_CONVB, K_CVTB, K_POOLB, K_STEMB, K_ROWSM, K_THIN, K_STEMP, K_PWPAIR, K_PW1, K_SC3, K_PW3, K_PANEL, K_PANELP, K_HALO, K_KSTREAM, K_CKSTREAM, K_BNECK1, K_BNECKT, K_CONVPW, K_CONVPWP, K_CONVPWO, K_ROWSAG };
+enum Kind { K_CONV, K_STEM, K_POOL, K_GDW, K_CONF, K_PRROI, K_PERM, K_DECODE, K_FORK, K_JOIN, K_ROWS, K_CONVB, K_CVTB, K_POOLB, K_STEMB, K_ROWSM, K_THIN, K_STEMP, K_PWPAIR, K_PW1, K_SC3, K_PW3, K_PANEL, K_PANELP, K_HALO, K_KSTREAM, K_CKSTREAM, K_BNECK1, K_BNECKT, K_CONVPW, K_CONVPWP, K_CONVPWO, K_ROWSAG, K_DECB, K_ROWSAGB, K_CROPB };
 
 constexpr int kLanes = 4;     // lane 0 is the caller's stream
 
@@ -172,6 +172,19 @@ int issue(Plan *pl, hipStream_t main_stream, bool lanes, hipEvent_t *marks = nul
             rc = usot_rows_append_gather_f32(s, fresh, bank, picked, &op.i[2], (const int32_t *)op.p[4], op.i[0], op.i[1]);
             break;
         }
+        case K_DECB:
+            rc = usot_decode_batch_f32(s, (const float *)op.p[0], (const float *)op.p[1], (const float *)op.p[2],
+                                       (const double *)op.p[3], (double *)op.p[4], op.i[0], op.i[1], op.i[2], op.i[3],
+                                       op.f[0], op.d[0], op.d[1], op.p[5], (float *)op.l[0]);
+            break;
+        case K_ROWSAGB: {
+            const float *fresh[4] = {(const float *)op.p[0], (const float *)op.p[1], (const float *)op.p[2], (const float *)op.p[3]};
+            float *bank[4] = {(float *)op.l[0], (float *)op.l[1], (float *)op.l[2], (float *)op.l[3]};
+            float *picked[3] = {(float *)op.l[4], (float *)op.l[5], (float *)op.l[6]};
+            rc = usot_rows_append_gather_batch_f32(s, fresh, bank, picked, &op.i[2], op.p[4], op.i[0], op.i[1], op.i[6]);
+            break;
+        }
+        case K_CROPB: rc = usot_crop_resize_batch_u8_f32(s, op.p[0], (float *)op.p[1], op.i[0], op.i[1]); break;
         case K_STEMB:
             rc = usot_stem_pool_lp(s, (const float *)op.p[0], op.p[1], (const float *)op.p[2], (void *)op.p[3], op.i[0], op.i[1],
                                    op.i[2], op.i[3], op.i[4], op.i[5], op.i[7], op.i[6], op.f[1], op.f[2], op.f[3]);
@@ -508,6 +521,54 @@ extern "C" int usot_plan_add_rows_append_gather(void *plan, const float *const *
     for (int i = 0; i < 3; ++i) op->l[4 + i] = (int64_t)(uintptr_t)picked[i];
     op->p[4] = idx_dev;
     op->i[0] = n_pick; op->i[1] = slot_pos;
+    return USOT_OK;
+}
+
+// lock-step multi-video tracking (csrc/multitrack.hip): the plan adders check their arguments as the eager entry points do
+extern "C" int usot_plan_add_decode_batch(void *plan, const float *cls, const float *cls_mem, const float *bbox, const double *window,
+                                          double *out, int B, int S, int instance_size, int stride, float ratio, double penalty_k,
+                                          double window_influence, const void *ctl, float *roi_out)
+{
+    if (!plan || !cls || !cls_mem || !bbox || !window || !out || !ctl || !roi_out || B < 1 || B > 65535 || S < 1 || S > 32)
+        return USOT_EINVAL;
+    Op *op = push(plan, K_DECB);
+    if (!op) return USOT_ESTATE;
+    op->p[0] = cls; op->p[1] = cls_mem; op->p[2] = bbox; op->p[3] = window; op->p[4] = out; op->p[5] = ctl;
+    op->l[0] = (int64_t)(uintptr_t)roi_out;
+    op->i[0] = B; op->i[1] = S; op->i[2] = instance_size; op->i[3] = stride;
+    op->f[0] = ratio; op->d[0] = penalty_k; op->d[1] = window_influence;
+    return USOT_OK;
+}
+
+extern "C" int usot_plan_add_rows_append_gather_batch(void *plan, const float *const *fresh, float *const *bank, float *const *picked,
+                                                      const int32_t *row_len, const void *ctl, int B, int n_pick, int bank_rows)
+{
+    if (!plan || !fresh || !bank || !picked || !row_len || !ctl || B < 1 || B > 65535 || n_pick < 1 || n_pick > 32 || bank_rows < 1)
+        return USOT_EINVAL;
+    for (int q = 0; q < 4; ++q) {
+        if (!fresh[q] || !bank[q] || row_len[q] <= 0 || (row_len[q] & 3)) return USOT_EINVAL;
+        if (q && !picked[q - 1]) return USOT_EINVAL;
+    }
+    Op *op = push(plan, K_ROWSAGB);
+    if (!op) return USOT_ESTATE;
+    for (int q = 0; q < 4; ++q) {
+        op->p[q] = fresh[q];
+        op->l[q] = (int64_t)(uintptr_t)bank[q];
+        op->i[2 + q] = row_len[q];
+    }
+    for (int q = 0; q < 3; ++q) op->l[4 + q] = (int64_t)(uintptr_t)picked[q];
+    op->p[4] = ctl;
+    op->i[0] = B; op->i[1] = n_pick; op->i[6] = bank_rows;
+    return USOT_OK;
+}
+
+extern "C" int usot_plan_add_crop_resize_batch(void *plan, const void *ctl, float *out, int B, int S)
+{
+    if (!plan || !ctl || !out || B < 1 || B > 65535 || S < 1 || S > 4096) return USOT_EINVAL;
+    Op *op = push(plan, K_CROPB);
+    if (!op) return USOT_ESTATE;
+    op->p[0] = ctl; op->p[1] = out;
+    op->i[0] = B; op->i[1] = S;
     return USOT_OK;
 }
 

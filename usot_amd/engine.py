@@ -1755,6 +1755,10 @@ class Engine:
         right after template(): it snapshots the current template encodes."""
         return Session(self, p, window, init_feats, capacity=getattr(self, 'session_capacity', 1024))
 
+    def open_batch_session(self, p, window, slots, capacity=1024, backbone_dtype=torch.float32):
+        """Device state of `slots` videos of one instance size that step together in one frame graph (see BatchSession)."""
+        return BatchSession(self, p, window, slots, capacity=capacity, backbone_dtype=backbone_dtype)
+
 
 class Session:
     """One video's state kept in HBM + its per-frame launch plan (a captured hipGraph).
@@ -2159,3 +2163,378 @@ class MemoryFeatures(object):
 
     def append(self, feat):
         self.session.append_feature(feat)
+
+
+# ---------------------------------------------------------------------------------------------------------- lock-step batch
+# One record per slot of a step's control block (include/usot_hip.h: usot_slot_rec), behind a STEP_HDR-byte header whose first
+# double is the step tag.
+STEP_HDR = 64
+SLOT_REC = np.dtype([('tsz', '<f8', (2,)), ('im', '<u8'), ('H', '<i4'), ('W', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('win', '<i4'),
+                     ('fill', '<i4', (3,)), ('append_row', '<i4'), ('next_row', '<i4'), ('picks', '<i4', (32,))])
+assert SLOT_REC.itemsize == 192 and SLOT_REC.fields['append_row'][1] == 56 and SLOT_REC.fields['picks'][1] == 64
+IDLE_TSZ = (64.0, 64.0)         # target size of a slot that sits a step out (its results are not read)
+
+
+def crop_fields(im_shape, pos, win, avg_chans):
+    """(x0, y0, win, fill) of a slot's crop record: the window origin in image coordinates (hostutils.crop_geometry, as
+    Session.frame_from_image computes it) and the padding colour (numpy's float -> uint8 assignment truncates)."""
+    from .hostutils import crop_geometry
+    (cx0, _, cy0, _), (top, _, left, _) = crop_geometry(im_shape, pos, win)
+    fill = np.asarray(avg_chans).astype(np.uint8)
+    return int(cx0) - left, int(cy0) - top, int(win), (int(fill[0]), int(fill[1]), int(fill[2]))
+
+
+class SlotBook(object):
+    """Host bookkeeping of a BatchSession's slots (no device work): which slots hold a video, how many memory features each has,
+    which pooled feature still waits for its bank row, and the control-block records of a step.
+
+    Each bank kind is ONE tensor [B * cap, row]; slot b's row r is global row b * cap + r (0 = init feature, 1 = its flip,
+    2 + i = memory feature i, cap - 1 = the slot's scratch row).  A step appends the PREVIOUS step's pooled feature of every
+    slot (at its start, before the gather that may pick it): to its row when it is pending, else to the scratch row."""
+
+    def __init__(self, slots, cap, nq):
+        self.B, self.cap, self.nq = int(slots), int(cap), int(nq)
+        if not 1 <= self.nq <= 32:
+            raise ValueError('mem_queue_size must be in 1..32 for a lock-step session; got %d' % self.nq)
+        self.active = [False] * self.B
+        self.n = [0] * self.B
+        self.pending = [False] * self.B
+        self.prev_row = [self.scratch(b) for b in range(self.B)]
+
+    def row(self, b, r):
+        return b * self.cap + r
+
+    def scratch(self, b):
+        return self.row(b, self.cap - 1)
+
+    def load(self, b):
+        """A new video in slot b: bank rows 0-2 are written by the caller, one memory feature; whatever the previous occupant
+        left pending goes to the scratch row."""
+        self.active[b], self.n[b], self.pending[b], self.prev_row[b] = True, 1, False, self.scratch(b)
+
+    def release(self, b):
+        self.active[b], self.n[b], self.pending[b], self.prev_row[b] = False, 0, False, self.scratch(b)
+
+    def free_slot(self):
+        for b in range(self.B):
+            if not self.active[b]:
+                return b
+        return None
+
+    def need_grow(self):
+        return any(a and 2 + n >= self.cap - 1 for a, n in zip(self.active, self.n))
+
+    def grow(self):
+        assert not any(self.pending), 'flush before growing'
+        self.cap *= 2
+        self.prev_row = [self.scratch(b) for b in range(self.B)]
+
+    def pack_idle(self, recs):
+        """Every slot idle: no crop, appends and picks on the scratch rows (warm-up replays, the flush plan's gather half)."""
+        for b in range(self.B):
+            r = recs[b]
+            r['tsz'] = IDLE_TSZ
+            r['im'] = 0
+            r['append_row'] = r['next_row'] = self.scratch(b)
+            r['picks'][:] = self.scratch(b)
+
+    def pack(self, recs, items, crops=None):
+        """Write the step's records.  items: {slot: (picks, tsz_scaled)} of the slots that step (picks: the N_q - 2 sampled
+        memory indices); crops: {slot: (im_addr, H, W, x0, y0, win, fill)} of the slots whose crop the kernel makes."""
+        crops = crops or {}
+        for b in range(self.B):
+            r = recs[b]
+            r['append_row'] = self.prev_row[b] if self.pending[b] else self.scratch(b)
+            it = items.get(b)
+            if it is None:
+                r['tsz'] = IDLE_TSZ
+                r['im'] = 0
+                r['next_row'] = self.scratch(b)
+                r['picks'][:] = self.scratch(b)
+                continue
+            if not self.active[b]:
+                raise ValueError('slot %d holds no video' % b)
+            picks, tsz = it
+            if len(picks) != self.nq - 2:
+                raise ValueError('%d sampled memory slots for a session built for mem_queue_size = %d' % (len(picks), self.nq))
+            pk = np.asarray(picks, np.int64)
+            if len(pk) and (pk.min() < 0 or pk.max() >= self.n[b]):
+                raise ValueError('slot %d: memory picks %s outside 0..%d' % (b, pk.tolist(), self.n[b] - 1))
+            r['tsz'] = (float(tsz[0]), float(tsz[1]))
+            r['picks'][:] = self.scratch(b)
+            r['picks'][0], r['picks'][1] = self.row(b, 0), self.row(b, 1)
+            r['picks'][2:self.nq] = self.row(b, 2) + pk
+            r['next_row'] = self.row(b, 2 + self.n[b])
+            c = crops.get(b)
+            if c is None:
+                r['im'] = 0
+            else:
+                r['im'], r['H'], r['W'], r['x0'], r['y0'], r['win'] = c[:6]
+                r['fill'] = c[6]
+
+    def stepped(self, items):
+        """After a step's tags: every pending feature was appended at the step's start; the stepping slots' new features are
+        pending (for the next step, or flush)."""
+        for b in range(self.B):
+            if b in items:
+                self.pending[b], self.prev_row[b] = True, self.row(b, 2 + self.n[b])
+                self.n[b] += 1
+            else:
+                self.pending[b], self.prev_row[b] = False, self.scratch(b)
+
+    def pack_flush(self, recs):
+        self.pack_idle(recs)
+        for b in range(self.B):
+            if self.pending[b]:
+                recs[b]['append_row'] = self.prev_row[b]
+
+    def flushed(self):
+        self.pending = [False] * self.B
+        self.prev_row = [self.scratch(b) for b in range(self.B)]
+
+
+class BatchSession:
+    """B videos ("slots") of one instance size in HBM + ONE captured frame graph that steps all of them (lock-step tracking).
+
+    A step (lanes = 0, nothing forked):
+        crop every slot's search window (one launch; a slot whose record names no image keeps what the host wrote) ->
+        encode the previous step's B pooled features (one conv_batch at n = B) -> append them to their bank rows and gather
+        every slot's N_q picked encodings (one launch) -> backbone at batch B -> heads at batch B -> decode B slots (one
+        launch, one result row + tag each) -> PrRoIPool of B winning boxes (one launch).
+    The backbone and heads are exact fp32 whatever the engine's split16_f32 (the graph has no range word); opt-in
+    backbone_dtype=torch.float16 puts the fp16 backbone with an fp32 neck in front of the same fp32 heads.  The step's control
+    block (STEP_HDR + B SLOT_REC records) and the result rows live in pinned host memory the kernels address directly."""
+
+    ROW = 7 * 7 * 256
+
+    def __init__(self, engine, p, window, slots, capacity=1024, backbone_dtype=torch.float32):
+        if backbone_dtype not in (torch.float32, torch.float16):
+            raise hip.HipError('BatchSession backbone_dtype: torch.float32 or torch.float16; got %s' % (backbone_dtype,))
+        self.e, self.p = engine, p
+        dev = engine.device
+        self.size, self.S = int(p.instance_size), int(p.score_size)
+        self.B = int(slots)
+        if self.B < 1:
+            raise hip.HipError('BatchSession needs at least one slot')
+        self.nq = int(getattr(p, 'mem_queue_size', 7))
+        if not 4 <= self.nq <= 32:
+            raise hip.HipError('mem_queue_size must be in 4..32 for a lock-step session; got %d' % self.nq)
+        self.backbone_dtype = backbone_dtype
+        self.opt = dict(engine.opt)
+        self.opt['split16_f32'] = False                 # exact fp32 arithmetic: the step graph has no range word
+        self.window = torch.from_numpy(np.ascontiguousarray(window, dtype=np.float64)).reshape(-1).to(dev)
+        self.book = SlotBook(self.B, capacity, self.nq)
+        cap = capacity
+        self.bank = torch.zeros(self.B * cap, 7, 7, 256, device=dev)
+        self.bank_enc = [torch.zeros(self.B * cap, hk, wk, 256, device=dev) for hk, wk in KGEO]
+        self.zk = [torch.zeros(self.B, hk, wk, 512, device=dev) for hk, wk in KGEO]
+        nbytes = STEP_HDR + self.B * SLOT_REC.itemsize
+        self.ctl = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
+        self._recs = self.ctl.numpy()[STEP_HDR:].view(SLOT_REC)
+        self._tag = self.ctl.numpy()[:8].view(np.float64)
+        self.fctl = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()       # the flush plan's block
+        self._frecs = self.fctl.numpy()[STEP_HDR:].view(SLOT_REC)
+        self.out = torch.zeros(self.B, 16, dtype=torch.float64).pin_memory()   # per slot: 8 results, the tag at [8]
+        self._out_np = self.out.numpy()
+        self._im_dev = [None] * self.B
+        self._im_host = [None] * self.B
+        self._step = 0
+        self._items = []
+        self._lenc = None
+        self._build()
+
+    @property
+    def cap(self):
+        return self.book.cap
+
+    def _append_gather(self, pl, fresh, ctl):
+        banks = [self.bank] + self.bank_enc
+        rl = [int(b[0].numel()) for b in banks]
+        hip.check(hip.lib().usot_plan_add_rows_append_gather_batch(
+            pl.h, (C.c_void_p * 4)(*[t.data_ptr() for t in fresh]), (C.c_void_p * 4)(*[t.data_ptr() for t in banks]),
+            (C.c_void_p * 3)(*[t.data_ptr() for t in self.mk]), (C.c_int32 * 4)(*rl), hip.ptr(ctl), self.B, self.nq,
+            int(self.bank.shape[0])), 'plan_add_rows_append_gather_batch')
+
+    def _build(self):
+        e, L, B, nq, p = self.e, hip.lib(), self.B, self.nq, self.p
+        bld = Builder(e.W, e.tuning, 0, self.opt)
+        pl = bld.plan
+        self.x = bld.buf(B, 3, self.size, self.size)
+        self.x.zero_()
+        self.feat = bld.buf(B, 7, 7, 256)
+        self.feat.zero_()
+        self.roi = bld.buf(B, 5)
+        self.mk = [bld.buf(B * nq, hk, wk, 256) for hk, wk in KGEO]
+        self.mem_in = bld.buf(1)                        # heads() only asks whether there is a memory branch
+        hip.check(L.usot_plan_add_crop_resize_batch(pl.h, hip.ptr(self.ctl), hip.ptr(self.x), B, self.size), 'plan_add_crop_resize_batch')
+        enc = bld.encode_kernel(self.feat, B, 256, 'mem')             # the previous step's B pooled features
+        self._append_gather(pl, [self.feat] + enc, self.ctl)
+        if self.backbone_dtype == torch.float16:
+            xf, hf = bld.backbone_bf16(self.x, B, self.size, dtype=torch.float16, neck_f32=True)
+        else:
+            xf, hf = bld.backbone(self.x, B, self.size, need_stem=False)
+        bbox, cls2, S = bld.heads(xf, B, hf, self.zk, self.mem_in, nq, mk=self.mk)
+        assert S == self.S, (S, self.S)
+        hip.check(L.usot_plan_add_decode_batch(pl.h, hip.ptr(cls2[0]), hip.ptr(cls2[1]), hip.ptr(bbox), hip.ptr(self.window),
+                                               hip.ptr(self.out), B, S, self.size, int(p.total_stride), float(p.ratio),
+                                               float(p.penalty_k), float(p.window_influence), hip.ptr(self.ctl),
+                                               hip.ptr(self.roi)), 'plan_add_decode_batch')
+        c = 256
+        hip.check(L.usot_plan_add_prroi(pl.h, hip.ptr(xf), hip.ptr(self.roi), hip.ptr(self.feat), B, c, hf, hf, 7, 7, 1.0,
+                                        hf * hf * c, 1, hf * c, c, 49 * c, 1, 7 * c, c), 'plan_add_prroi')
+        if bld.ovf is not None:
+            raise hip.HipError('BatchSession: the step graph has a split-fp16 range word')
+        # flush(): the same encode launch (n = B) and the same append kernel, reading its own control block
+        fb = Builder(e.W, e.tuning, 0, self.opt)
+        fenc = fb.encode_kernel(self.feat, B, 256, 'mem')
+        self._append_gather(fb.plan, [self.feat] + fenc, self.fctl)
+        fb.plan.keep += fenc + [self.feat, self.fctl, self.bank] + self.bank_enc + self.mk
+        self._flush_plan = fb.plan
+        pl.keep += enc + self.mk + self.bank_enc + self.zk + [self.bank, self.ctl, self.window, self.out, self.roi, self.feat]
+        self.xf, self.cls2, self.bbox, self.hf, self.plan, self.log = xf, cls2, bbox, hf, pl, bld.log
+        # warm-up replay (Engine._finish): every slot idle, appends to the scratch rows
+        self.book.pack_idle(self._recs)
+        self._tag[0] = -1.0
+        e._finish(pl)
+        torch.cuda.current_stream().synchronize()
+        self.feat.zero_()
+        torch.cuda.current_stream().synchronize()
+
+    def _encode_rows(self, rows):
+        """Encode bank rows `rows` (global, 3 of them) into bank_enc on the exact-fp32 encoders."""
+        if self._lenc is None:
+            bld = Builder(self.e.W, self.e.tuning, 0, self.opt)
+            src = bld.buf(3, 7, 7, 256)
+            enc = bld.encode_kernel(src, 3, 256, 'mem')
+            self._lenc = (bld.plan, src, enc)
+        plan, src, enc = self._lenc
+        src.copy_(self.bank[rows[0]:rows[-1] + 1])
+        plan.run()
+        for g in range(3):
+            self.bank_enc[g][rows[0]:rows[-1] + 1].copy_(enc[g])
+
+    def load(self, slot, zf, init_feats):
+        """A new video in `slot`: its template kernels (Engine.encode_template at n = 1 of zf, NCHW-shaped [1,256,7,7]) and the
+        memory seeds - bank rows 0, 1, 2 = init feature, its flip, init feature again as memory 0 - with their encodings."""
+        if not 0 <= slot < self.B:
+            raise hip.HipError('slot %d of %d' % (slot, self.B))
+        if self.book.pending[slot]:
+            self.flush()
+        zk = self.e.encode_template(zf)['zk']
+        for g in range(3):
+            self.zk[g][slot].copy_(zk[g][0])
+        base = self.book.row(slot, 0)
+        for i, f in enumerate((init_feats[0], init_feats[1], init_feats[0])):
+            self.bank[base + i].copy_(hip.to_nhwc(_as_dev_f32(f, self.e.device))[0])
+        self._encode_rows([base, base + 1, base + 2])
+        self.book.load(slot)
+
+    def release(self, slot):
+        self.book.release(slot)
+
+    def _grow(self):
+        self.flush()
+        torch.cuda.current_stream().synchronize()
+        old, B, dev = self.book.cap, self.B, self.e.device
+        new = old * 2
+
+        def regrow(t):
+            g = torch.zeros((B * new,) + tuple(t.shape[1:]), device=dev)
+            g.view(B, new, -1)[:, :old].copy_(t.view(B, old, -1))
+            return g
+        self.bank = regrow(self.bank)
+        self.bank_enc = [regrow(t) for t in self.bank_enc]
+        self.book.grow()
+        self._build()
+
+    def submit(self, items):
+        """Enqueue one step on the current stream.  items: {slot: dict(picks=N_q - 2 memory indices, tsz=target size x scale_z,
+        and either image=uint8 HWC frame + pos, win (python2round(s_x)), avg_chans - cropped on the device - or crop=CHW float
+        tensor, or neither: the crop already in x[slot] is used)}.  Active slots that are not listed sit the step out.  Pair with
+        collect()."""
+        for b in items:
+            if not (0 <= b < self.B and self.book.active[b]):
+                raise hip.HipError('slot %r holds no video' % (b,))
+        if self.book.need_grow():
+            self._grow()
+        crops, book_items = {}, {}
+        for b, it in items.items():
+            book_items[b] = (it['picks'], it['tsz'])
+            if it.get('image') is not None:
+                im = it['image']
+                h, w, _ = im.shape
+                if self._im_dev[b] is None or tuple(self._im_dev[b].shape) != (h, w, 3):
+                    self._im_dev[b] = torch.empty((h, w, 3), dtype=torch.uint8, device=self.e.device)
+                    self._im_host[b] = torch.empty((h, w, 3), dtype=torch.uint8).pin_memory()
+                np.copyto(self._im_host[b].numpy(), im)
+                self._im_dev[b].copy_(self._im_host[b], non_blocking=True)
+                crops[b] = (self._im_dev[b].data_ptr(), h, w) + crop_fields(im.shape, it['pos'], it['win'], it['avg_chans'])
+            elif it.get('crop') is not None:
+                self.x[b].copy_(torch.as_tensor(it['crop']).reshape(3, self.size, self.size))
+        self.book.pack(self._recs, book_items, crops)
+        self._step += 1
+        self._tag[0] = float(self._step)
+        self._stream = st = torch.cuda.current_stream()
+        hip.check(hip.lib().usot_plan_run(self.plan.h, C.c_void_p(st.cuda_stream)), 'usot_plan_run')
+        self._items = list(items)
+
+    def collect(self):
+        """Wait for every slot's tag of the submitted step; {slot: float64[8]} (Session.collect's layout) of the slots that
+        stepped."""
+        out, tag = self._out_np, self._tag[0]
+        tags = out[:, 8]
+        spin_until = time.perf_counter() + self.e.opt['spin_seconds']
+        while not (tags == tag).all() and time.perf_counter() < spin_until:
+            pass
+        if not (tags == tag).all():
+            deadline = time.monotonic() + 20.0
+            while not (tags == tag).all() and time.monotonic() < deadline:
+                time.sleep(5e-5)
+            if not (tags == tag).all():
+                self._stream.synchronize()
+                if not (tags == tag).all():
+                    bad = int(np.nonzero(tags != tag)[0][0])
+                    raise hip.HipError('frame %r never published its result block (tag reads %r): '
+                                       'the frame graph did not run to the decode kernel' % (tag, float(tags[bad])))
+        res = {b: out[b, :8].copy() for b in self._items}
+        self.book.stepped(res)
+        return res
+
+    def step(self, items):
+        self.submit(items)
+        return self.collect()
+
+    def flush(self):
+        """Append every pending pooled feature to its bank row NOW (otherwise the next step's graph does it): the same encode
+        launch (n = B) and the same append kernel as the step graph, so the same bits."""
+        if not any(self.book.pending):
+            return
+        self.book.pack_flush(self._frecs)
+        st = torch.cuda.current_stream()
+        hip.check(hip.lib().usot_plan_run(self._flush_plan.h, C.c_void_p(st.cuda_stream)), 'usot_plan_run')
+        st.synchronize()
+        self.book.flushed()
+
+    def memory_feature(self, slot, i):
+        """Memory feature i of `slot` as an NCHW-shaped view [1,256,7,7] of its bank row."""
+        if self.book.pending[slot] and i == self.book.n[slot] - 1:
+            self.flush()
+        r = self.book.row(slot, 2 + i)
+        return self.bank[r:r + 1].permute(0, 3, 1, 2)
+
+
+class SlotMemory(object):
+    """Session-like view of one BatchSession slot, for MemoryFeatures."""
+
+    def __init__(self, bs, slot):
+        self.bs, self.slot = bs, slot
+
+    @property
+    def n(self):
+        return self.bs.book.n[self.slot]
+
+    def memory_feature(self, i):
+        return self.bs.memory_feature(self.slot, i)
+
+    def append_feature(self, feat):
+        raise hip.HipError('lock-step sessions take memory features from their step graph only')

@@ -30,6 +30,8 @@ EXPORTS = (
     'usot_plan_profile', 'usot_plan_op_info', 'usot_rows_copy_f32', 'usot_plan_add_rows_copy', 'usot_crop_resize_u8_f32', 'usot_conv_resolve_tile', 'usot_decode_dev_f32',
     'PrRoIPoolingForwardGpu', 'usot_groupdw_auto_variant',
     'usot_stem_pool_ind_f32', 'usot_plan_add_stem_pool_ind', 'usot_bw_probe', 'usot_conv_kstream_lp', 'usot_conv_kstream_supported', 'usot_plan_add_conv_kstream', 'usot_pw_kstream_lp', 'usot_pw_kstream_supported', 'usot_plan_add_pw_kstream', 'usot_conv3x3_halo_lp', 'usot_conv3x3_halo_supported', 'usot_plan_add_conv3x3_halo', 'usot_bneck_first_lp', 'usot_bneck_first_supported', 'usot_plan_add_bneck_first', 'usot_bneck_tail_lp', 'usot_bneck_tail_supported', 'usot_plan_add_bneck_tail', 'usot_pw_panel_lp', 'usot_pw_panel_supported', 'usot_pw_panel_pixels', 'usot_pw_panel_min_pixels', 'usot_plan_add_pw_panel', 'usot_pw_panel_pair_lp', 'usot_pw_panel_pair_supported', 'usot_plan_add_pw_panel_pair', 'usot_conv_pw_lp', 'usot_conv_pw_supported', 'usot_conv_pw_pixels', 'usot_plan_add_conv_pw', 'usot_conv_pw_pair_lp', 'usot_conv_pw_pair_supported', 'usot_plan_add_conv_pw_pair', 'usot_conv_pw_ov_lp', 'usot_conv_pw_ov_supported', 'usot_conv_pw_ov_ws_bytes', 'usot_plan_add_conv_pw_ov', 'usot_conv_pw_ov_trace', 'usot_stem_conv_mu_f32', 'usot_stem_pool_mu_f32', 'usot_plan_add_stem_pool_mu', 'usot_plan_add_stem_mu', 'usot_pw_pair_lp', 'usot_pw_pair_layout', 'usot_pw_pair_supported', 'usot_plan_add_pw_pair', 'usot_pw_pair_f32', 'usot_pw_pair_f32s', 'usot_pw_pair_f32s_supported', 'usot_pw_pair_f32_supported', 'usot_pw_pair_f32_ws_floats', 'usot_pw_single_f32', 'usot_pw_single_f32_supported', 'usot_plan_add_pw_single', 'usot_stream_conv3x3_f32', 'usot_stream_conv3x3_f32_supported', 'usot_plan_add_stream_conv3x3', 'usot_pw_triple_f32', 'usot_pw_triple_f32_supported', 'usot_plan_add_pw_triple',
+    'usot_decode_batch_f32', 'usot_plan_add_decode_batch', 'usot_rows_append_gather_batch_f32', 'usot_plan_add_rows_append_gather_batch',
+    'usot_crop_resize_batch_u8_f32', 'usot_plan_add_crop_resize_batch',
 )
 
 
@@ -159,6 +161,12 @@ def lib():
         L.usot_rows_append_gather_f32.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int]
         L.usot_plan_add_rows_append_gather.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int]
         L.usot_crop_resize_u8_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 9
+        L.usot_decode_batch_f32.argtypes = [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float] + [C.c_double] * 2 + [C.c_void_p] * 2
+        L.usot_plan_add_decode_batch.argtypes = [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float] + [C.c_double] * 2 + [C.c_void_p] * 2
+        L.usot_rows_append_gather_batch_f32.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3
+        L.usot_plan_add_rows_append_gather_batch.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3
+        L.usot_crop_resize_batch_u8_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 2
+        L.usot_plan_add_crop_resize_batch.argtypes = [C.c_void_p] * 3 + [C.c_int] * 2
         L.usot_plan_add_conv_bf16.argtypes = [C.c_void_p, C.c_void_p]
         L.usot_plan_add_conv_lp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.usot_pw_pair_lp.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -817,3 +825,38 @@ def crop_resize(frame_u8, out, x0, y0, win, fill):
     check(lib().usot_crop_resize_u8_f32(stream(), ptr(frame_u8), ptr(out), H, W_, int(x0), int(y0), int(win), S,
                                         int(fill[0]), int(fill[1]), int(fill[2])), 'usot_crop_resize_u8_f32')
     return out
+
+
+# ---- lock-step multi-video tracking (csrc/multitrack.hip; the control block is engine.STEP_CTL / SLOT_REC)
+def decode_batch(cls, cls_mem, bbox, window, out, ctl, roi, S, instance_size, stride, ratio, penalty_k, window_influence):
+    """cls / cls_mem [B,S,S] float32, bbox [B,4,S,S], window [S,S] float64 (device); out float64 [B,16] and roi float32 [B,5]
+    (device or pinned); ctl: the step's control block (pinned or device uint8).  B = out.shape[0]."""
+    for t in (cls, cls_mem, bbox, window, out, roi, ctl):
+        if not t.is_contiguous():
+            raise HipError('decode_batch needs dense tensors')
+    B = out.shape[0]
+    check(lib().usot_decode_batch_f32(stream(), ptr(cls), ptr(cls_mem), ptr(bbox), ptr(window), ptr(out), B, int(S),
+                                      int(instance_size), int(stride), float(ratio), float(penalty_k), float(window_influence),
+                                      ptr(ctl), ptr(roi)), 'usot_decode_batch_f32')
+    return out
+
+
+def rows_append_gather_batch(fresh, banks, picked, ctl, n_pick):
+    """fresh: 4 tensors [B, ...]; banks: 4 tensors [B*cap, ...]; picked: 3 tensors [B*n_pick, ...] (float32, dense, device)."""
+    B = fresh[0].shape[0]
+    rl = [int(b[0].numel()) for b in banks]
+    check(lib().usot_rows_append_gather_batch_f32(
+        stream(), (C.c_void_p * 4)(*[t.data_ptr() for t in fresh]), (C.c_void_p * 4)(*[t.data_ptr() for t in banks]),
+        (C.c_void_p * 3)(*[t.data_ptr() for t in picked]), (C.c_int32 * 4)(*rl), ptr(ctl), B, int(n_pick), int(banks[0].shape[0])),
+        'usot_rows_append_gather_batch_f32')
+
+
+def crop_resize_batch(ctl, out):
+    """out: device float32 [B,3,S,S]; each slot's image address and window come from its control-block record."""
+    _dev(out)
+    if not out.is_contiguous():
+        raise HipError('crop_resize_batch needs a dense [B,3,S,S] output')
+    check(lib().usot_crop_resize_batch_u8_f32(stream(), ptr(ctl), ptr(out), out.shape[0], out.shape[-1]),
+          'usot_crop_resize_batch_u8_f32')
+    return out
+

@@ -130,6 +130,17 @@ class USOTTracker(object):
     # ------------------------------------------------------------------ init
     def init(self, im, target_pos, target_sz, model):
         """usot_tracker.py:22-131."""
+        state = self.init_state(im, target_pos, target_sz, model)
+        if self.fused and hasattr(model, 'engine') and _dev_of(model).type == 'cuda':
+            from .engine import MemoryFeatures
+            state['session'] = model.engine.open_session(state['p'], state['window'], state['init_features'])
+            state['memory_features'] = MemoryFeatures(state['session'])      # list-like view of the device bank
+        return state
+
+    def init_state(self, im, target_pos, target_sz, model):
+        """init() without a device session: the yaml overlay, the 255 / 271 choice, the template (crop + PrRoIPool template,
+        left in force on the model as model.zf) and the memory seeds from the init crop and its flip.  Shared by init() and
+        multitrack.MultiVideoTracker.add()."""
         model.pr_pool = True
         dev = _dev_of(model)
         p = USOTConfig()
@@ -172,10 +183,6 @@ class USOTTracker(object):
         state['init_features'] = feats
         state['memory_features'] = [feats[0]]
         state['memory_confidences'] = [0.9]
-        if self.fused and hasattr(model, 'engine') and dev.type == 'cuda':
-            from .engine import MemoryFeatures
-            state['session'] = model.engine.open_session(p, window, feats)
-            state['memory_features'] = MemoryFeatures(state['session'])      # list-like view of the device bank
         return state
 
     def _flipped(self, img, box):
