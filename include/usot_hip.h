@@ -367,6 +367,18 @@ int usot_maxpool3x3s2_f32(void *stream, const float *x, float *y,
 int usot_xcorr_depthwise_f32(void *stream, const float *x, const float *k, float *out,
                              int P, int Hx, int Wx, int Hk, int Wk);
 
+/* ---- its two gradients (csrc/xcorr_grad.hip), dout [P][Hx-Hk+1][Wx-Wk+1]:
+ *   dx[p][a][b] = scale * sum_uv dout[p][a-u][b-v] * k[p][u][v]      (terms outside dout are 0)
+ *   dk[p][u][v] = scale * sum_ij dout[p][i][j]     * x[p][i+u][j+v]
+ * Every element is written once with a plain store (no atomics, no memset, no workspace) and every sum has a
+ * fixed order: equal inputs give equal bits.  5x5 / 3x5 / 5x3 templates with Wx <= 64 run one wavefront per
+ * plane (two planes per wavefront when Wx <= 32); anything else takes a one-thread-per-element kernel.
+ * Same argument checks as the forward; P == 0 is a no-op.                                              */
+int usot_xcorr_depthwise_bwd_x_f32(void *stream, const float *dout, const float *k, float *dx,
+                                   int P, int Hx, int Wx, int Hk, int Wk, float scale);
+int usot_xcorr_depthwise_bwd_k_f32(void *stream, const float *dout, const float *x, float *dk,
+                                   int P, int Hx, int Wx, int Hk, int Wk, float scale);
+
 /* ---- fused GroupDW on NHWC (connect.py:86-102): three depthwise xcorrs and the
  * softmax(weight)-weighted sum in one pass, no intermediate maps.
  *   branch b: x_b NHWC [XS][OH+hk_b-1][OW+wk_b-1] (pixel stride x_cs, channel offset x_co)

@@ -1,0 +1,102 @@
+"""torch.autograd bindings of the native depthwise cross-correlation (reference lib/models/connect.py:86-102,147-157).
+
+Forward values are `usot_amd.hip.xcorr_depthwise`'s, bit for bit; the gradients come from the two kernels of
+csrc/xcorr_grad.hip.  First-order gradients only, fp32 only, device tensors only (no CPU implementation: CPU
+tensors raise `hip.HipError`).
+"""
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import hip
+
+
+class XCorrDepthwiseFunction(torch.autograd.Function):
+    """out[b][c] = x[b][c] (*) kernel[b][c] (valid cross-correlation, one template per plane)."""
+
+    @staticmethod
+    def forward(ctx, x, kernel):
+        ctx.save_for_backward(x, kernel)
+        return hip.xcorr_depthwise(x, kernel)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        x, kernel = ctx.saved_tensors
+        dx = dk = None
+        if ctx.needs_input_grad[0]:
+            dx = hip.xcorr_depthwise_backward_x(dout, kernel, x.shape)
+        if ctx.needs_input_grad[1]:
+            dk = hip.xcorr_depthwise_backward_k(dout, x, kernel.shape)
+        return dx, dk
+
+
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+
+
+def xcorr_depthwise(x, kernel):
+    """Differentiable drop-in for the reference's `xcorr_depthwise` on NCHW device tensors."""
+    if _wants_grad(x, kernel):
+        hip._dev(x), hip._dev(kernel)
+        return XCorrDepthwiseFunction.apply(x, kernel)
+    return hip.xcorr_depthwise(x, kernel)
+
+
+def _groupdw_forward(zs, xs, weight):
+    w = torch.softmax(weight.detach(), 0)
+    wl = w.tolist()                      # host copies: the gradient kernels take the branch weight as a scalar argument
+    out = hip.xcorr_depthwise(xs[0], zs[0]).mul_(wl[0])
+    for i in (1, 2):
+        out.add_(hip.xcorr_depthwise(xs[i], zs[i]).mul_(wl[i]))
+    return out, w, wl
+
+
+class GroupDWFunction(torch.autograd.Function):
+    """sum_i softmax(weight)[i] * xcorr(x_i, z_i).  The branch weights reach the gradient kernels as `scale`, and the
+    gradient of `weight` is rebuilt from s_i = <dout, xcorr(x_i, z_i)> = <dk_i at scale 1, z_i>: no correlation map
+    is saved."""
+
+    @staticmethod
+    def forward(ctx, weight, z0, z1, z2, x0, x1, x2):
+        zs, xs = (z0, z1, z2), (x0, x1, x2)
+        out, w, ctx.wl = _groupdw_forward(zs, xs, weight)
+        ctx.save_for_backward(w, *zs, *xs)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        w, zs, xs = ctx.saved_tensors[0], ctx.saved_tensors[1:4], ctx.saved_tensors[4:7]
+        need_w = ctx.needs_input_grad[0]
+        wl = ctx.wl
+        dz, dx, s = [None] * 3, [None] * 3, []
+        for i in range(3):
+            if ctx.needs_input_grad[4 + i]:
+                dx[i] = hip.xcorr_depthwise_backward_x(dout, zs[i], xs[i].shape, wl[i])
+            if need_w:
+                dk1 = hip.xcorr_depthwise_backward_k(dout, xs[i], zs[i].shape)
+                s.append((dk1 * zs[i]).sum(dtype=torch.float64))
+                if ctx.needs_input_grad[1 + i]:
+                    dz[i] = dk1.mul_(w[i])
+            elif ctx.needs_input_grad[1 + i]:
+                dz[i] = hip.xcorr_depthwise_backward_k(dout, xs[i], zs[i].shape, wl[i])
+        dweight = None
+        if need_w:
+            s = torch.stack(s)                                       # float64: three numbers
+            w64 = w.double()
+            dweight = (w64 * (s - (w64 * s).sum())).to(w.dtype)      # softmax Jacobian, (diag(w) - w w^T) s
+        return (dweight, *dz, *dx)
+
+
+def groupdw(z, x, weight):
+    """The reference's `GroupDW.forward`: `z`, `x` triples of NCHW device tensors (templates / search maps of the
+    5x5, 3x5 and 5x3 branches), `weight` the three branch logits."""
+    zs, xs = tuple(z), tuple(x)
+    if len(zs) != 3 or len(xs) != 3:
+        raise ValueError('groupdw: three templates and three search maps expected')
+    for t in zs + xs:
+        hip._dev(t)
+    hip._dev(weight)
+    if _wants_grad(weight, *zs, *xs):
+        return GroupDWFunction.apply(weight, *zs, *xs)
+    return _groupdw_forward(zs, xs, weight)[0]

@@ -18,6 +18,8 @@ if EXPERIMENTS:
 # per-file flags.  xcorr.hip: hipcc's SLP vectoriser packs the depthwise FMAs into v_pk_fma_f32 pairs, which
 # on gfx950 run at the scalar-FMA rate but need operand pairs in adjacent registers: the LDS-DMA GroupDW
 # kernel goes from 109 VGPRs to 256 + spills with it
+# xcorr_grad.hip keeps the default: there the vectoriser packs 46 of the unit's 124 FMAs into 23 v_pk_fma_f32 and changes
+# nothing else in the ISA (75 / 82 VGPRs for the 5x5 kernels either way, no scratch, 516 v_mov_b32 in both)
 FILE_FLAGS = {'xcorr.hip': ['-fno-slp-vectorize'],
               'conv_igemm.hip': ['-std=c++20']}      # templated lambda over the producer's register buffers
 

@@ -1015,6 +1015,8 @@ extern "C" int usot_abi_version(void) { return 6; }   // 2: usot_conv_desc.w_fra
 // symbols added at 6 (no existing signature changed): the lock-step batch of csrc/multitrack.hip - usot_decode_batch_f32,
 // usot_rows_append_gather_batch_f32, usot_crop_resize_batch_u8_f32 and their plan adders (usot_plan_add_decode_batch,
 // usot_plan_add_rows_append_gather_batch, usot_plan_add_crop_resize_batch)
+// and the gradients of the plane xcorr in csrc/xcorr_grad.hip - usot_xcorr_depthwise_bwd_x_f32, usot_xcorr_depthwise_bwd_k_f32.
+// Still 6: adding symbols breaks no caller, and the version is what callers compare for equality.
 
 extern "C" const char *usot_strerror(int code)
 {

@@ -32,6 +32,7 @@ EXPORTS = (
     'usot_stem_pool_ind_f32', 'usot_plan_add_stem_pool_ind', 'usot_bw_probe', 'usot_conv_kstream_lp', 'usot_conv_kstream_supported', 'usot_plan_add_conv_kstream', 'usot_pw_kstream_lp', 'usot_pw_kstream_supported', 'usot_plan_add_pw_kstream', 'usot_conv3x3_halo_lp', 'usot_conv3x3_halo_supported', 'usot_plan_add_conv3x3_halo', 'usot_bneck_first_lp', 'usot_bneck_first_supported', 'usot_plan_add_bneck_first', 'usot_bneck_tail_lp', 'usot_bneck_tail_supported', 'usot_plan_add_bneck_tail', 'usot_pw_panel_lp', 'usot_pw_panel_supported', 'usot_pw_panel_pixels', 'usot_pw_panel_min_pixels', 'usot_plan_add_pw_panel', 'usot_pw_panel_pair_lp', 'usot_pw_panel_pair_supported', 'usot_plan_add_pw_panel_pair', 'usot_conv_pw_lp', 'usot_conv_pw_supported', 'usot_conv_pw_pixels', 'usot_plan_add_conv_pw', 'usot_conv_pw_pair_lp', 'usot_conv_pw_pair_supported', 'usot_plan_add_conv_pw_pair', 'usot_conv_pw_ov_lp', 'usot_conv_pw_ov_supported', 'usot_conv_pw_ov_ws_bytes', 'usot_plan_add_conv_pw_ov', 'usot_conv_pw_ov_trace', 'usot_stem_conv_mu_f32', 'usot_stem_pool_mu_f32', 'usot_plan_add_stem_pool_mu', 'usot_plan_add_stem_mu', 'usot_pw_pair_lp', 'usot_pw_pair_layout', 'usot_pw_pair_supported', 'usot_plan_add_pw_pair', 'usot_pw_pair_f32', 'usot_pw_pair_f32s', 'usot_pw_pair_f32s_supported', 'usot_pw_pair_f32_supported', 'usot_pw_pair_f32_ws_floats', 'usot_pw_single_f32', 'usot_pw_single_f32_supported', 'usot_plan_add_pw_single', 'usot_stream_conv3x3_f32', 'usot_stream_conv3x3_f32_supported', 'usot_plan_add_stream_conv3x3', 'usot_pw_triple_f32', 'usot_pw_triple_f32_supported', 'usot_plan_add_pw_triple',
     'usot_decode_batch_f32', 'usot_plan_add_decode_batch', 'usot_rows_append_gather_batch_f32', 'usot_plan_add_rows_append_gather_batch',
     'usot_crop_resize_batch_u8_f32', 'usot_plan_add_crop_resize_batch',
+    'usot_xcorr_depthwise_bwd_x_f32', 'usot_xcorr_depthwise_bwd_k_f32',
 )
 
 
@@ -218,6 +219,8 @@ def lib():
         L.usot_stem_conv_f32.argtypes = [C.c_void_p] * 5 + [C.c_int] * 5
         L.usot_maxpool3x3s2_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6
         L.usot_xcorr_depthwise_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5
+        L.usot_xcorr_depthwise_bwd_x_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float]
+        L.usot_xcorr_depthwise_bwd_k_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float]
         L.usot_conf_fusion_reduce_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4
         L.usot_prroi_pool_forward_f32.argtypes = ([C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_float]
                                                   + [C.c_int64] * 8)
@@ -511,6 +514,46 @@ def xcorr_depthwise(x, kernel):
     check(lib().usot_xcorr_depthwise_f32(stream(), ptr(x), ptr(k), ptr(out), b * c, hx, wx, hk, wk),
           'usot_xcorr_depthwise_f32')
     return out
+
+
+def _xcorr_grad_geometry(what, dout, hx, wx, hk, wk):
+    if hk < 1 or wk < 1 or hx < hk or wx < wk or tuple(dout.shape[2:]) != (hx - hk + 1, wx - wk + 1):
+        raise HipError('%s: grad_output %s does not belong to a %dx%d map and a %dx%d template'
+                       % (what, tuple(dout.shape), hx, wx, hk, wk))
+
+
+def xcorr_depthwise_backward_x(dout, kernel, x_shape, scale=1.0):
+    """Gradient of `xcorr_depthwise` w.r.t. its search map, times `scale`: dout [B][C][OH][OW], kernel [B][C][Hk][Wk]
+    -> dx of shape `x_shape` ([B][C][Hx][Wx]).  Every element of dx is written by the kernel."""
+    _dev(dout), _dev(kernel)
+    b, c, hx, wx = (int(v) for v in x_shape)
+    hk, wk = kernel.shape[2], kernel.shape[3]
+    _xcorr_grad_geometry('xcorr_depthwise_backward_x', dout, hx, wx, hk, wk)
+    d = dout.contiguous().view(-1, dout.shape[2], dout.shape[3])
+    k = kernel.contiguous().view(-1, hk, wk)
+    if not d.shape[0] == k.shape[0] == b * c:
+        raise HipError('xcorr_depthwise_backward_x: plane counts differ (%d, %d vs %d)' % (d.shape[0], k.shape[0], b * c))
+    dx = torch.empty((b, c, hx, wx), device=dout.device, dtype=torch.float32)
+    check(lib().usot_xcorr_depthwise_bwd_x_f32(stream(), ptr(d), ptr(k), ptr(dx), b * c, hx, wx, hk, wk, float(scale)),
+          'usot_xcorr_depthwise_bwd_x_f32')
+    return dx
+
+
+def xcorr_depthwise_backward_k(dout, x, kernel_shape, scale=1.0):
+    """Gradient of `xcorr_depthwise` w.r.t. its template, times `scale`: dout [B][C][OH][OW], x [B][C][Hx][Wx]
+    -> dk of shape `kernel_shape` ([B][C][Hk][Wk]).  Every element of dk is written by the kernel."""
+    _dev(dout), _dev(x)
+    b, c, hk, wk = (int(v) for v in kernel_shape)
+    hx, wx = x.shape[2], x.shape[3]
+    _xcorr_grad_geometry('xcorr_depthwise_backward_k', dout, hx, wx, hk, wk)
+    d = dout.contiguous().view(-1, dout.shape[2], dout.shape[3])
+    xs = x.contiguous().view(-1, hx, wx)
+    if not d.shape[0] == xs.shape[0] == b * c:
+        raise HipError('xcorr_depthwise_backward_k: plane counts differ (%d, %d vs %d)' % (d.shape[0], xs.shape[0], b * c))
+    dk = torch.empty((b, c, hk, wk), device=dout.device, dtype=torch.float32)
+    check(lib().usot_xcorr_depthwise_bwd_k_f32(stream(), ptr(d), ptr(xs), ptr(dk), b * c, hx, wx, hk, wk, float(scale)),
+          'usot_xcorr_depthwise_bwd_k_f32')
+    return dk
 
 
 def groupdw_desc(xs, zs, out, wsm, *, S, x_rep, OH, OW, Cc, x_cs, x_co, z_cs, z_co, cols=0):

@@ -6,6 +6,8 @@ reference lib/models/models.py:298-306, modules.py:61-135, connect.py:12-74,
 104-121, 160-219, 284-292) and record each convolution's geometry so that
 `usot_amd.engine` can lower the graph to HIP launches.  Calling `forward` on a
 holder raises: there is deliberately no torch fallback for the tensor math.
+The one exception is `GroupDWSlots.forward`, which hands its tensors to the differentiable HIP
+binding of `usot_amd.autograd` (device tensors only).
 """
 import torch
 import torch.nn as nn
@@ -147,6 +149,12 @@ class GroupDWSlots(nn.Module):
     def __init__(self):
         super().__init__()
         self.weight = nn.Parameter(torch.ones(3), requires_grad=False)
+
+    def forward(self, z, x):
+        """reference connect.py:86-102 on triples of NCHW device tensors; differentiable (usot_amd.autograd.groupdw).  The
+        inference engine does not come through here: it runs the fused NHWC kernel on this parameter."""
+        from . import autograd
+        return autograd.groupdw(z, x, self.weight)
 
 
 class ConfFusionSlots(nn.Module):
