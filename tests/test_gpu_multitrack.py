@@ -12,6 +12,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import guarded  # noqa: E402
 from usot_amd import hip, synth  # noqa: E402
 from usot_amd.engine import SLOT_REC, STEP_HDR, Engine, crop_fields  # noqa: E402
 from usot_amd.io_utils import cxy_wh_2_rect  # noqa: E402
@@ -50,10 +51,18 @@ def _bits(a):
     return np.ascontiguousarray(a).view(np.int64 if a.dtype == np.float64 else np.int32)
 
 
+@pytest.fixture
+def guards():
+    """The guarded.alloc / guarded.put buffers a kernel test hands to the raw entry points are checked, and forgotten, when the
+    test ends - also when one of its own assertions failed first."""
+    with guarded.patched():
+        yield
+
+
 # ------------------------------------------------------------------------------------------------------------- kernels
 @pytest.mark.parametrize('B', [1, 3, 8])
 @pytest.mark.parametrize('S', [25, 27])
-def test_decode_batch_bitwise_vs_decode_dev(S, B):
+def test_decode_batch_bitwise_vs_decode_dev(S, B, guards):
     g = np.random.default_rng(100 * S + B)
     cls = g.standard_normal((B, S, S)).astype(np.float32)
     cm = g.standard_normal((B, S, S)).astype(np.float32)
@@ -76,8 +85,8 @@ def test_decode_batch_bitwise_vs_decode_dev(S, B):
     wd = torch.from_numpy(window).reshape(-1).to(DEV)
     p = USOTConfig()
     size = 255 if S == 25 else 271
-    out = torch.zeros(B, 16, dtype=torch.float64, device=DEV)
-    roi = torch.zeros(B, 5, device=DEV)
+    out = guarded.alloc((B, 16), torch.float64, DEV, 'zero')            # outputs handed to the raw entry points: between canaries
+    roi = guarded.alloc((B, 5), torch.float32, DEV, 'zero')
     dcls, dcm, dbox = (torch.from_numpy(a).to(DEV) for a in (cls, cm, bbox))
     hip.decode_batch(dcls, dcm, dbox, wd, out, torch.from_numpy(ctl).to(DEV), roi, S, size, 8, p.ratio, p.penalty_k,
                      p.window_influence)
@@ -85,8 +94,8 @@ def test_decode_batch_bitwise_vs_decode_dev(S, B):
     for b in range(B):
         c8 = torch.zeros(8, dtype=torch.float64, device=DEV)
         c8[0], c8[1], c8[6] = float(recs[b]['tsz'][0]), float(recs[b]['tsz'][1]), 41.0
-        ref = torch.zeros(10, dtype=torch.float64, device=DEV)
-        rroi = torch.zeros(5, device=DEV)
+        ref = guarded.alloc((10,), torch.float64, DEV, 'zero')
+        rroi = guarded.alloc((5,), torch.float32, DEV, 'zero')
         hip.check(hip.lib().usot_decode_dev_f32(hip.stream(), hip.ptr(dcls[b]), hip.ptr(dcm[b]), hip.ptr(dbox[b]), hip.ptr(wd),
                                                 hip.ptr(ref), S, size, 8, C.c_float(p.ratio), C.c_double(p.penalty_k),
                                                 C.c_double(p.window_influence), hip.ptr(c8), hip.ptr(rroi)), 'decode_dev')
@@ -100,13 +109,13 @@ def test_decode_batch_bitwise_vs_decode_dev(S, B):
             assert int(o[b, 0]) == 9 * S + 3
 
 
-def test_append_gather_batch_vs_torch_indexing():
+def test_append_gather_batch_vs_torch_indexing(guards):
     B, cap, nq = 3, 10, 7
     lens = [7 * 7 * 256, 5 * 5 * 256, 3 * 5 * 256, 5 * 3 * 256]
     g = torch.Generator().manual_seed(5)
-    banks = [torch.randn(B * cap, n, generator=g).to(DEV) for n in lens]
+    banks = [guarded.put(torch.randn(B * cap, n, generator=g), DEV) for n in lens]
     fresh = [torch.randn(B, n, generator=g).to(DEV) for n in lens]
-    picked = [torch.full((B * nq, n), float('nan'), device=DEV) for n in lens[1:]]
+    picked = [guarded.alloc((B * nq, n), torch.float32, DEV, 'full', float('nan')) for n in lens[1:]]
     ctl, recs = _ctl(B)
     app = [4, 19, 25]                                 # slot 1 appends to its scratch row (nothing pending)
     picks = [[0, 1, 2, 3, 4, 4, 2],                   # the appended row, twice
@@ -127,7 +136,7 @@ def test_append_gather_batch_vs_torch_indexing():
             assert torch.equal(picked[k - 1], wp), k
 
 
-def test_crop_batch_vs_single_crop():
+def test_crop_batch_vs_single_crop(guards):
     im, _ = synth.frame(5, t=3)
     im2, _ = synth.frame(9, h=240, w=320, t=1)
     S = 255
@@ -144,10 +153,10 @@ def test_crop_batch_vs_single_crop():
         x0, y0, w_, fill = crop_fields(img.shape, pos, win, avg)
         recs[b]['im'], recs[b]['H'], recs[b]['W'] = d.data_ptr(), img.shape[0], img.shape[1]
         recs[b]['x0'], recs[b]['y0'], recs[b]['win'], recs[b]['fill'] = x0, y0, w_, fill
-        ref = torch.empty(3, S, S, device=DEV)
+        ref = guarded.alloc((3, S, S), torch.float32, DEV)
         hip.crop_resize(d, ref, x0, y0, w_, fill)
         refs.append(ref)
-    out = torch.full((B, 3, S, S), -7.0, device=DEV)
+    out = guarded.alloc((B, 3, S, S), torch.float32, DEV, 'full', -7.0)
     hip.crop_resize_batch(torch.from_numpy(ctl).to(DEV), out)
     for b in range(len(cases)):
         assert torch.equal(out[b], refs[b]), cases[b][1:]

@@ -11,10 +11,36 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+import guarded  # noqa: E402
 import usot_oracle as orc  # noqa: E402
-from usot_amd import hip  # noqa: E402
+from usot_amd import autograd, hip  # noqa: E402
 
 DEV = 'cuda:0'
+
+
+@pytest.fixture(autouse=True)
+def _memory_guard():
+    """Every output a wrapper of usot_amd.hip / usot_amd.autograd allocates starts as NaN and sits between canaries
+    (tests/guarded.py); the guards are checked when the test ends."""
+    with guarded.patched(hip, autograd):
+        yield
+
+
+def _shape(args):
+    return tuple(args[0]) if len(args) == 1 and not isinstance(args[0], int) else tuple(args)
+
+
+def g_empty(*shape, dtype=torch.float32):
+    """torch.empty on the device, between canaries and NaN-filled: for buffers a test hands to a raw entry point itself"""
+    return guarded.alloc(_shape(shape), dtype, DEV)
+
+
+def g_zeros(*shape, dtype=torch.float32):
+    return guarded.alloc(_shape(shape), dtype, DEV, 'zero')
+
+
+def g_full(shape, value, dtype=torch.float32):
+    return guarded.alloc(tuple(shape), dtype, DEV, 'full', value)
 
 
 def rel_err(got, ref):
@@ -121,7 +147,7 @@ def test_split_fp16_tiles_range_contract(tile):
     # the plain epilogue, the in-launch split-K combine and the split-K slabs alike; in range it stays 0
     for act in (hip.ACT_RELU, hip.ACT_CONF):
         for ks in (1, 3):
-            ovf = torch.zeros(1, dtype=torch.int32, device=DEV)
+            ovf = g_zeros(1, dtype=torch.int32)
             hip.conv2d(xd, wd, bd, KH=k, KW=k, pad=(1, 1), tile=tile, ksplit=ks, act=act, ovf=ovf)
             assert int(ovf.item()) == 0, (act, ks)
             y = hip.conv2d(xo, wd, bd, KH=k, KW=k, pad=(1, 1), tile=tile, ksplit=ks, act=act, ovf=ovf)
@@ -131,7 +157,7 @@ def test_split_fp16_tiles_range_contract(tile):
             assert int(ovf.item()) == 1                      # sticky: only the reader clears it
     xi = xd.clone()
     xi[0, 5, 5, 3] = float('inf')                            # a non-finite INPUT is reported too
-    ovf = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ovf = g_zeros(1, dtype=torch.int32)
     hip.conv2d(xi, wd, bd, KH=k, KW=k, pad=(1, 1), tile=tile, act=hip.ACT_RELU, ovf=ovf)
     assert int(ovf.item()) == 1
 
@@ -155,7 +181,7 @@ def test_split_maps_chain_two_convolutions_without_an_fp32_map(tile2):
     assert rel_err(hip.unsplit_map(y1).permute(0, 3, 1, 2).cpu().numpy(), r1.float().numpy()) < 2e-5
     w2p, sc = hip.split16_pack(pack_w(w2).to(DEV))
     b2d = b2.to(DEV)
-    y2 = torch.empty(N, H, W, 2 * Cc, device=DEV)
+    y2 = g_empty(N, H, W, 2 * Cc)
     mk = lambda tile, xs: hip.conv_desc(y1.data_ptr(), w2p.data_ptr(), b2d.data_ptr(), y2.data_ptr(), N=N, H=H, W=W, Cin=Cc, OH=H, OW=W,
                                         Cout=2 * Cc, KH=3, KW=3, pad=(1, 1), tile=tile, w_frag=2, w_scale=sc.data_ptr(), x_split=xs)
     hip.check(hip.lib().usot_conv2d_f32(hip.stream(), C.byref(mk(tile2, 1))), 'usot_conv2d_f32')
@@ -192,7 +218,7 @@ def test_conv_deferred_reduction_feeds_the_fused_pair(tile, ks):
     ref = F.conv2d(x, w, None, 1, 2, 2)
     xd, wd, bd = x.permute(0, 2, 3, 1).contiguous().to(DEV), pack_w(w).to(DEV), b.to(DEV)
     M = N * H * H
-    ws = torch.zeros(ks * M * Cout + 4096, device=DEV)
+    ws = g_zeros(ks * M * Cout + 4096)
     d = hip.conv_desc(xd.data_ptr(), wd.data_ptr(), None, xd.data_ptr(), N=N, H=H, W=H, Cin=Cin, OH=H, OW=H, Cout=Cout, KH=3, KW=3,
                       pad=(2, 2), dil=(2, 2), tile=tile, ksplit=ks, ws=ws.data_ptr(), defer=1)
     hip.check(hip.lib().usot_conv2d_f32(hip.stream(), C.byref(d)), 'conv (deferred)')
@@ -214,7 +240,7 @@ def test_conv_deferred_reduction_feeds_the_fused_pair(tile, ks):
         t2_sum += slabs[q]                                                     # the kernel's order: part 0, 1, ... then the bias
     t2_sum = (t2_sum + bd).relu().contiguous()
     for t2, parts in ((slabs, ks), (t2_sum, 0)):
-        y = torch.empty(M, CO, device=DEV); t = torch.empty(M, CN, device=DEV)
+        y = g_empty(M, CO); t = g_empty(M, CN)
         wsp = hip.pw_pair_f32_ws(M, Cout, CO, CN, DEV)
         pd = hip.pw_pair_desc(t2.data_ptr(), w3p.data_ptr(), b3d.data_ptr(), res.data_ptr(), y.data_ptr(), w1p.data_ptr(), b1d.data_ptr(),
                               t.data_ptr(), M, Cout, CO, CN, hip.ACT_RELU, wsp.data_ptr() if wsp is not None else None,
@@ -230,7 +256,7 @@ def test_conv_deferred_reduction_feeds_the_fused_pair(tile, ks):
     rsum = ((rparts[0] + rparts[1]) + rparts[2] + rbias).contiguous()
     outs = []
     for rr, parts in ((rparts, 3), (rsum, 0)):
-        y = torch.empty(M, CO, device=DEV); t = torch.empty(M, CN, device=DEV)
+        y = g_empty(M, CO); t = g_empty(M, CN)
         wsp = hip.pw_pair_f32_ws(M, Cout, CO, CN, DEV)
         pd = hip.pw_pair_desc(t2_sum.data_ptr(), w3p.data_ptr(), b3d.data_ptr(), rr.data_ptr(), y.data_ptr(), w1p.data_ptr(), b1d.data_ptr(),
                               t.data_ptr(), M, Cout, CO, CN, hip.ACT_RELU, wsp.data_ptr() if wsp is not None else None,
@@ -260,7 +286,7 @@ def test_conv_streamk_batch_of_problems(tile):
         if res is not None:
             ref = F.relu(ref + res.permute(0, 1, 4, 2, 3))
         xd, wd, bd = x.permute(0, 1, 3, 4, 2).contiguous().to(DEV), pack_w(w).to(DEV), b.to(DEV)
-        y = torch.full((G, N, OH, OW, Cout), float('nan'), device=DEV)
+        y = g_full((G, N, OH, OW, Cout), float('nan'))
         rd = res.to(DEV) if res is not None else None
         descs.append(hip.conv_desc(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), y.data_ptr(), N=N, H=H, W=W, Cin=Cin, OH=OH, OW=OW, Cout=Cout,
                                    KH=3, KW=3, pad=pad, dil=dil, res=rd.data_ptr() if rd is not None else None,
@@ -295,8 +321,8 @@ def test_conv_activations():
 
 
 def test_conv_rejects_bad_geometry():
-    x = torch.zeros(1, 5, 5, 48, device=DEV)                 # Cin not a multiple of 32
-    w = torch.zeros(16, 48 * 9, device=DEV)
+    x = g_zeros(1, 5, 5, 48)                 # Cin not a multiple of 32
+    w = g_zeros(16, 48 * 9)
     with pytest.raises(hip.HipError):
         hip.conv2d(x, w, None, KH=3, KW=3)
     with pytest.raises(hip.HipError):
@@ -327,6 +353,10 @@ def test_stem_and_maxpool(size, n):
 
 XC = [(29, 29, 5, 5), (27, 29, 3, 5), (29, 27, 5, 3), (31, 31, 5, 5), (33, 31, 5, 3), (12, 9, 4, 2),
       (64, 64, 5, 5), (70, 70, 5, 5), (7, 7, 7, 7)]
+# dispatch edges of the plane kernels: Wx 32 | 33 (two planes per wavefront | one), Wx 64 | 65 (specialised | generic), OH = 1 and
+# OW = 1 on the specialised templates, a single output
+XC_EDGES = [(9, 32, 5, 5), (9, 33, 5, 5), (9, 64, 5, 3), (9, 65, 5, 3), (5, 29, 5, 5), (29, 5, 5, 5), (3, 5, 3, 5)]
+XC = XC + XC_EDGES
 
 
 @pytest.mark.parametrize('hx,wx,hk,wk', XC)
@@ -385,8 +415,8 @@ def test_groupdw_three_segments_one_launch(cols):
     zk = [torch.randn(b, hk, wk, 512, generator=g).to(DEV) for hk, wk in geo]
     mk = [torch.randn(b * m, hk, wk, 256, generator=g).to(DEV) for hk, wk in geo]
     w_reg, w_cls = torch.softmax(torch.randn(3, generator=g), 0).numpy(), torch.softmax(torch.randn(3, generator=g), 0).numpy()
-    outs = [torch.full((b, OW, OW, 256), float('nan'), device=DEV), torch.full((b, OW, OW, 256), float('nan'), device=DEV),
-            torch.full((b * m, OW, OW, 256), float('nan'), device=DEV)]
+    outs = [g_full((b, OW, OW, 256), float('nan')), g_full((b, OW, OW, 256), float('nan')),
+            g_full((b * m, OW, OW, 256), float('nan'))]
     mk_desc = lambda xs, zs, out, wsm, S, rep, x_co, z_cs: hip.groupdw_desc(
         [t.data_ptr() for t in xs], [t.data_ptr() for t in zs], out.data_ptr(), wsm, S=S, x_rep=rep, OH=OW, OW=OW, Cc=256,
         x_cs=[512] * 3, x_co=[x_co] * 3, z_cs=[z_cs] * 3, z_co=[x_co if z_cs == 512 else 0] * 3, cols=cols)
@@ -433,7 +463,7 @@ def test_prroi_pool_vs_c_oracle(layout):
     # same float32 operation order as the restated .cu: agree to a few ulp
     assert np.max(np.abs(got - ref.numpy())) < 2e-6 * max(1.0, float(ref.abs().max()))
     assert np.all(got[3] == 0) and np.all(got[6] == 0)        # zero-width roi, fully outside roi
-    empty = hip.prroi_pool(fd, torch.zeros(0, 5, device=DEV), 7, 7, 1.0)
+    empty = hip.prroi_pool(fd, g_zeros(0, 5), 7, 7, 1.0)
     assert tuple(empty.shape) == (0, 256, 7, 7)
 
 
@@ -530,7 +560,7 @@ def test_pw_pair_f32_split_fp16_operands(M):
     t2w = t2.clone(); t2w[:, ::7] *= 1e-4; t2w[:, 3::11] *= 300.0
     y64 = F.relu(t2w.double() @ w3.double().t() + b3.double() + res.double())
     t64 = F.relu(y64 @ w1.double().t() + b1.double())
-    ovf = torch.zeros(1, dtype=torch.int32, device=DEV)
+    ovf = g_zeros(1, dtype=torch.int32)
     y, t = hip.pw_pair_f32(d(t2w).reshape(1, 1, M, cm), *args[1:], split16=True, ovf=ovf)
     assert rel_err(y.reshape(M, co).cpu().numpy(), y64.numpy()) < 1e-5 and rel_err(t.reshape(M, cn).cpu().numpy(), t64.numpy()) < 1e-5
     assert int(ovf.item()) == 0
@@ -641,7 +671,7 @@ def test_prroi_feature_gradient_vs_oracles(seed, shape, n):
     ww = ex.prroi_pool_exact_backward(f.shape, rois[wide.numpy()], g.numpy()[wide.numpy()], 7, 7, 1.0)
     assert np.max(np.abs(gw - ww)) < 2.5e-5 * max(1.0, float(np.abs(ww).max()))
     # an empty RoI list gives a zero gradient of the right shape
-    z = hip.prroi_pool_backward(f.shape, torch.zeros(0, 5, device=DEV), torch.zeros(0, shape[1], 7, 7, device=DEV), 7, 7, 1.0)
+    z = hip.prroi_pool_backward(f.shape, g_zeros(0, 5), g_zeros(0, shape[1], 7, 7), 7, 7, 1.0)
     assert tuple(z.shape) == tuple(f.shape) and not z.any()
 
 
@@ -700,10 +730,10 @@ def test_prroi_gradient_reference_symbols_exact_signature():
     fd, rd, gd = f.to(DEV), torch.from_numpy(rois).to(DEV), g.to(DEV)
     top = hip.prroi_pool(fd, rd, 7, 7, 1.0)
     L = hip.lib()
-    gin = torch.full(f.shape, 3.0, device=DEV)                               # must be overwritten, not accumulated into
+    gin = g_full(f.shape, 3.0)                               # must be overwritten, not accumulated into
     L.PrRoIPoolingBackwardGpu(hip.stream(), hip.ptr(fd), hip.ptr(rd), hip.ptr(top), hip.ptr(gd), hip.ptr(gin),
                               24, 15, 17, 7, 7, C.c_float(1.0), top.numel(), gin.numel())
-    gr = torch.full((n, 5), 3.0, device=DEV)
+    gr = g_full((n, 5), 3.0)
     L.PrRoIPoolingCoorBackwardGpu(hip.stream(), hip.ptr(fd), hip.ptr(rd), hip.ptr(top), hip.ptr(gd), hip.ptr(gr),
                                   24, 15, 17, 7, 7, C.c_float(1.0), top.numel(), gr.numel())
     torch.cuda.synchronize()
@@ -712,7 +742,7 @@ def test_prroi_gradient_reference_symbols_exact_signature():
     assert np.max(np.abs(gin.cpu().numpy() - ref_f)) < 1e-5 * max(1.0, float(np.abs(ref_f).max()))
     assert np.max(np.abs(gr.cpu().numpy() - ref_r)) < 3e-5 * max(1.0, float(np.abs(ref_r).max()))
     # inconsistent counts are refused: a line on stderr, nothing written, no exit
-    keep = torch.full((n, 5), 9.0, device=DEV)
+    keep = g_full((n, 5), 9.0)
     L.PrRoIPoolingCoorBackwardGpu(hip.stream(), hip.ptr(fd), hip.ptr(rd), hip.ptr(top), hip.ptr(gd), hip.ptr(keep),
                                   24, 15, 17, 7, 7, C.c_float(1.0), top.numel(), keep.numel() - 5)
     torch.cuda.synchronize()
@@ -729,7 +759,7 @@ def test_prroi_reference_symbol_exact_signature():
     rois = torch.tensor(ROIS, dtype=torch.float32)
     ref = orc.prroi_pool(f, rois, 7, 7, 1.0)
     fd, rd = f.to(DEV), rois.to(DEV)
-    out = torch.zeros(len(ROIS), 48, 7, 7, device=DEV)                     # at::zeros in the binding
+    out = g_zeros(len(ROIS), 48, 7, 7)                     # at::zeros in the binding
     L = hip.lib()
     L.PrRoIPoolingForwardGpu(hip.stream(), hip.ptr(fd), hip.ptr(rd), hip.ptr(out), 48, 15, 17, 7, 7,
                              C.c_float(1.0), out.numel())
@@ -737,13 +767,13 @@ def test_prroi_reference_symbol_exact_signature():
     got = out.cpu().numpy()
     assert np.max(np.abs(got - ref.numpy())) < 2e-6 * max(1.0, float(ref.abs().max()))
     # spatial_scale is applied to the roi, pooled size is free
-    out2 = torch.zeros(len(ROIS), 48, 3, 5, device=DEV)
+    out2 = g_zeros(len(ROIS), 48, 3, 5)
     L.PrRoIPoolingForwardGpu(hip.stream(), hip.ptr(fd), hip.ptr(rd), hip.ptr(out2), 48, 15, 17, 3, 5,
                              C.c_float(0.5), out2.numel())
     ref2 = orc.prroi_pool(f, rois, 3, 5, 0.5)
     assert np.max(np.abs(out2.cpu().numpy() - ref2.numpy())) < 2e-6 * max(1.0, float(ref2.abs().max()))
     # a top_count that is not a whole number of RoIs is refused (stderr line, no launch, no exit)
-    out3 = torch.full((3, 48, 7, 7), 7.0, device=DEV)
+    out3 = g_full((3, 48, 7, 7), 7.0)
     L.PrRoIPoolingForwardGpu(hip.stream(), hip.ptr(fd), hip.ptr(rd), hip.ptr(out3), 48, 15, 17, 7, 7,
                              C.c_float(1.0), out3.numel() - 1)
     torch.cuda.synchronize()
@@ -901,7 +931,7 @@ def test_device_crop_matches_host_crop(pos, win):
     size = 255
     want, _ = hostutils.get_subwindow_tracking(im, np.array(pos), size, win, avg)
     (cx0, _, cy0, _), (top, _, left, _) = hostutils.crop_geometry(im.shape, pos, win)
-    out = torch.empty(3, size, size, device=DEV)
+    out = g_empty(3, size, size)
     hip.crop_resize(torch.from_numpy(np.ascontiguousarray(im)).to(DEV), out, int(cx0) - left, int(cy0) - top, win, avg.astype(np.uint8))
     assert torch.equal(out.cpu(), want)
 
@@ -920,9 +950,9 @@ def test_conv_batch_heterogeneous():
         b = torch.randn(128, generator=g)
         refs.append(F.relu(F.conv2d(x, w, b, 1, 0, dil)))
         wd, bd = pack_w(w).to(DEV), b.to(DEV)
-        y = torch.empty(1, oh, ow, 128, device=DEV)
+        y = g_empty(1, oh, ow, 128)
         ks = 3 if i == 1 else 1
-        ws = torch.zeros(ks * oh * ow * 128 + ((oh * ow + 15) // 16) * 4, device=DEV) if ks > 1 else None   # slabs + tile tickets
+        ws = g_zeros(ks * oh * ow * 128 + ((oh * ow + 15) // 16) * 4) if ks > 1 else None   # slabs + tile tickets
         descs.append(hip.conv_desc(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), y.data_ptr(), N=1, H=31, W=31, Cin=256,
                                    OH=oh, OW=ow, Cout=128, KH=3, KW=3, dil=dil, act=hip.ACT_RELU, tile=31 if i == 0 else 0,
                                    ksplit=ks, ws=ws.data_ptr() if ws is not None else None))
@@ -937,10 +967,10 @@ def test_conv_batch_heterogeneous():
 def test_rows_copy_gather_scatter():
     bank = torch.randn(16, 64, device=DEV)
     idx = torch.tensor([3, 0, 15, 7], dtype=torch.int32, device=DEV)
-    out = torch.zeros(4, 64, device=DEV)
+    out = g_zeros(4, 64)
     hip.check(hip.lib().usot_rows_copy_f32(hip.stream(), hip.ptr(bank), hip.ptr(idx), hip.ptr(out), 4, 64, 0), 'gather')
     assert torch.equal(out, bank[idx.long()])
-    dst = torch.zeros(16, 64, device=DEV)
+    dst = g_zeros(16, 64)
     hip.check(hip.lib().usot_rows_copy_f32(hip.stream(), hip.ptr(out), hip.ptr(idx), hip.ptr(dst), 4, 64, 1), 'scatter')
     want = torch.zeros(16, 64, device=DEV)
     want[idx.long()] = out
@@ -958,8 +988,8 @@ def test_plan_run_capture_and_lanes():
     xd = x.permute(0, 2, 3, 1).contiguous().to(DEV)
     w1d, w2d = pack_w(w1).to(DEV), pack_w(w2).to(DEV)
     for lanes in (False, True):
-        y1 = torch.zeros(1, 20, 20, 64, device=DEV)
-        y2 = torch.zeros(1, 20, 20, 64, device=DEV)
+        y1 = g_zeros(1, 20, 20, 64)
+        y2 = g_zeros(1, 20, 20, 64)
         plan = C.c_void_p(L.usot_plan_create())
         d1 = hip.conv_desc(xd.data_ptr(), w1d.data_ptr(), None, y1.data_ptr(), N=1, H=20, W=20, Cin=64, OH=20, OW=20,
                            Cout=64, KH=3, KW=3, pad=(1, 1), act=hip.ACT_RELU)
@@ -997,10 +1027,10 @@ def test_decode_dev_writes_roi_and_tag(gold_host):
     cls, cm, bbox = gold_host[c + '/cls'], gold_host[c + '/cls_mem'], gold_host[c + '/bbox']
     tsz, sz = gold_host[c + '/tsz'], float(gold_host[c + '/scale_z'])
     window = torch.from_numpy(np.outer(np.hanning(S), np.hanning(S))).reshape(-1).to(DEV)
-    ctl = torch.zeros(8, dtype=torch.float64, device=DEV)
+    ctl = g_zeros(8, dtype=torch.float64)
     ctl[0], ctl[1], ctl[6] = tsz[0] * sz, tsz[1] * sz, 42.0
-    out = torch.zeros(9, dtype=torch.float64, device=DEV)
-    roi = torch.zeros(5, device=DEV)
+    out = g_zeros(9, dtype=torch.float64)
+    roi = g_zeros(5)
     dcls, dcm, dbox = torch.from_numpy(cls).to(DEV), torch.from_numpy(cm).to(DEV), torch.from_numpy(bbox).to(DEV)
     hip.check(hip.lib().usot_decode_dev_f32(hip.stream(), hip.ptr(dcls), hip.ptr(dcm),
                                             hip.ptr(dbox), hip.ptr(window), hip.ptr(out), S, 255, 8,
@@ -1083,8 +1113,8 @@ def test_thin_conv3x3_prediction_heads(n, hw):
     bc = torch.randn(2, generator=g)
     xd = x.permute(0, 1, 3, 4, 2).contiguous().to(DEV)
     wbd, wcd, bbd, bcd = pack_w(wb).to(DEV), pack_w(wc).to(DEV), bb.to(DEV), bc.to(DEV)
-    yb = torch.empty(n, 4, hw, hw, device=DEV)
-    yc = torch.empty(2, n, 1, hw, hw, device=DEV)
+    yb = g_empty(n, 4, hw, hw)
+    yc = g_empty(2, n, 1, hw, hw)
     gs = n * hw * hw * 256
     descs = [hip.conv_desc(xd[0].data_ptr(), wbd.data_ptr(), bbd.data_ptr(), yb.data_ptr(), N=n, H=hw, W=hw, Cin=256, OH=hw, OW=hw,
                            Cout=4, KH=3, KW=3, pad=(1, 1), act=hip.ACT_EXP, y_nchw=1),
@@ -1097,7 +1127,7 @@ def test_thin_conv3x3_prediction_heads(n, hw):
     for gi in range(2):
         ref = F.conv2d(x[1 + gi], wc[gi:gi + 1], bc[gi:gi + 1], 1, 1)
         assert rel_err(yc[gi].cpu().numpy(), ref.numpy()) < 1e-5
-    yb2, yc2 = torch.zeros_like(yb), torch.zeros_like(yc)
+    yb2, yc2 = g_zeros(yb.shape), g_zeros(yc.shape)
     descs2 = [hip.conv_desc(xd[0].data_ptr(), wbd.data_ptr(), bbd.data_ptr(), yb2.data_ptr(), N=n, H=hw, W=hw, Cin=256, OH=hw, OW=hw,
                             Cout=4, KH=3, KW=3, pad=(1, 1), act=hip.ACT_EXP, y_nchw=1, tile=70),
               hip.conv_desc(xd[1].data_ptr(), wcd.data_ptr(), bcd.data_ptr(), yc2.data_ptr(), N=n, H=hw, W=hw, Cin=256, OH=hw, OW=hw,
@@ -1117,15 +1147,15 @@ def test_rows_copy_multi_gather_scatter_and_stash():
     lens = [64, 128, 32, 256]
     banks = [torch.randn(12, n, device=DEV) for n in lens]
     idx = torch.tensor([5, 0, 11, 7, 9, 1234, -77], dtype=torch.int32, device=DEV)   # 4 rows + the three stashed entries
-    outs = [torch.zeros(4, n, device=DEV) for n in lens]
-    stash = torch.zeros(4, dtype=torch.int32, device=DEV)
+    outs = [g_zeros(4, n) for n in lens]
+    stash = g_zeros(4, dtype=torch.int32)
     pp = lambda ts: (C.c_void_p * 4)(*[t.data_ptr() for t in ts])
     rl = (C.c_int32 * 4)(*lens)
     hip.check(hip.lib().usot_rows_copy_multi_f32(hip.stream(), 4, pp(banks), hip.ptr(idx), pp(outs), 4, rl, 0, hip.ptr(stash)), 'gather')
     for b, o in zip(banks, outs):
         assert torch.equal(o, b[idx[:4].long()])
     assert stash.tolist() == [9, 1234, -77, 0]
-    dsts = [torch.zeros(12, n, device=DEV) for n in lens]
+    dsts = [g_zeros(12, n) for n in lens]
     hip.check(hip.lib().usot_rows_copy_multi_f32(hip.stream(), 3, pp(outs), hip.ptr(idx), pp(dsts), 4, rl, 1, None), 'scatter')
     for k, (o, d) in enumerate(zip(outs, dsts)):
         want = torch.zeros_like(d)
@@ -1153,7 +1183,7 @@ def test_rows_append_gather(pinned):
         nq = len(picks)
         idx_h = torch.tensor(picks + [-5, 123, 456, slot], dtype=torch.int32)          # slot_pos = nq + 3, as in the control block
         idx = idx_h.pin_memory() if pinned else idx_h.to(DEV)
-        picked = [torch.full((nq, n), -1.0, device=DEV) for n in lens[1:]]
+        picked = [g_full((nq, n), -1.0) for n in lens[1:]]
         p4 = lambda ts: (C.c_void_p * 4)(*[t.data_ptr() for t in ts])
         p3 = (C.c_void_p * 3)(*[t.data_ptr() for t in picked])
         hip.check(hip.lib().usot_rows_append_gather_f32(hip.stream(), p4(fresh), p4(banks), p3, (C.c_int32 * 4)(*lens),
@@ -1217,7 +1247,7 @@ def test_pw_panel_lp_expansion_conv(K, N, M, res, act, dtype):
         ref = ref.relu()
     xd, wd, bd = x.to(DEV), w.to(DEV), b.to(DEV)
     rd = r.to(DEV) if res else None
-    y = torch.full((M + 3, N), 7.0, dtype=dtype, device=DEV)         # three guard rows behind the output
+    y = g_full((M + 3, N), 7.0, dtype=dtype)         # three guard rows behind the output
     assert hip.lib().usot_pw_panel_supported(K, N) == 1 and hip.lib().usot_pw_panel_supported(K, N + 64) == 0
     hip.check(hip.lib().usot_pw_panel_lp(hip.stream(), hip.ptr(xd), hip.ptr(wd), hip.ptr(bd), hip.ptr(rd) if res else None, hip.ptr(y),
                                          M, K, N, act, 1 if dtype == torch.float16 else 0), 'usot_pw_panel_lp')
@@ -1226,7 +1256,7 @@ def test_pw_panel_lp_expansion_conv(K, N, M, res, act, dtype):
     tol = 2 ** -8 if dtype == torch.bfloat16 else 2 ** -11           # one rounding of the output
     assert float(((got - ref).abs() / ref.abs().clamp_min(1.0)).max()) <= tol * 1.01
     # the tiled kernel on the same operands (NHWC with H = M, W = 1)
-    y2 = torch.empty(M, N, dtype=dtype, device=DEV)
+    y2 = g_empty(M, N, dtype=dtype)
     d = hip.conv_desc(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), y2.data_ptr(), N=1, H=M, W=1, Cin=K, OH=M, OW=1, Cout=N, KH=1, KW=1,
                       res=rd.data_ptr() if res else None, act=act, tile=11)
     hip.check(hip.lib().usot_conv2d_lp(hip.stream(), C.byref(d), 1 if dtype == torch.float16 else 0, 0), 'usot_conv2d_lp')
@@ -1251,18 +1281,18 @@ def test_pw_panel_pair_equals_the_two_convolutions(cm, co, cn, M, act2, dtype):
     dt = 1 if dtype == torch.float16 else 0
     dev = lambda a: a.to(DEV)
     t2d, w3d, w1d, b3d, b1d, resd = map(dev, (t2, w3, w1, b3, b1, res))
-    y = torch.full((M + 2, co), 3.0, dtype=dtype, device=DEV)
-    t = torch.full((M + 2, cn), 3.0, dtype=dtype, device=DEV)
+    y = g_full((M + 2, co), 3.0, dtype=dtype)
+    t = g_full((M + 2, cn), 3.0, dtype=dtype)
     d = hip.pw_pair_desc(t2d.data_ptr(), w3d.data_ptr(), b3d.data_ptr(), resd.data_ptr(), y.data_ptr(), w1d.data_ptr(), b1d.data_ptr(),
                          t.data_ptr(), M, cm, co, cn, act2)
     assert hip.lib().usot_pw_panel_pair_supported(cm, co, cn) == 1
     hip.check(hip.lib().usot_pw_panel_pair_lp(hip.stream(), C.byref(d), dt), 'usot_pw_panel_pair_lp')
     assert torch.all(y[M:] == 3.0) and torch.all(t[M:] == 3.0)
-    y2 = torch.empty(M, co, dtype=dtype, device=DEV)
+    y2 = g_empty(M, co, dtype=dtype)
     d1 = hip.conv_desc(t2d.data_ptr(), w3d.data_ptr(), b3d.data_ptr(), y2.data_ptr(), N=1, H=M, W=1, Cin=cm, OH=M, OW=1, Cout=co, KH=1, KW=1,
                        res=resd.data_ptr(), act=1, tile=11)
     hip.check(hip.lib().usot_conv2d_lp(hip.stream(), C.byref(d1), dt, 0), 'conv3')
-    tt = torch.empty(M, cn, dtype=dtype, device=DEV)
+    tt = g_empty(M, cn, dtype=dtype)
     d2 = hip.conv_desc(y2.data_ptr(), w1d.data_ptr(), b1d.data_ptr(), tt.data_ptr(), N=1, H=M, W=1, Cin=co, OH=M, OW=1, Cout=cn, KH=1, KW=1,
                        act=act2, tile=11)
     hip.check(hip.lib().usot_conv2d_lp(hip.stream(), C.byref(d2), dt, 0), 'conv1')
@@ -1303,7 +1333,7 @@ def test_conv_pw_fused_equals_the_two_launches(n, h, pad, dil, dtype, form, rs):
     dt = 1 if dtype == torch.float16 else 0
     t1d, w2d, w3d, b2d, b3d, resd = (a.to(DEV) for a in (t1, w2, w3, b2, b3, res))
     assert hip.lib().usot_conv_pw_supported(cin, cm, co) == 1 and hip.lib().usot_conv_pw_supported(cin, 64, co) == 0
-    y = torch.full((M + 2, co), 5.0, dtype=dtype, device=DEV)
+    y = g_full((M + 2, co), 5.0, dtype=dtype)
     d = hip.conv_desc(t1d.data_ptr(), w2d.data_ptr(), b2d.data_ptr(), None, N=n, H=h, W=h, Cin=cin, OH=h, OW=h, Cout=cm, KH=3, KW=3,
                       pad=(pad, pad), dil=(dil, dil), act=1, tile=form | (0 if rs else 4))
     assert hip.lib().usot_conv_pw_pixels(M) == 128 and hip.lib().usot_conv_pw_pixels(192 * 256) == 256
@@ -1313,11 +1343,11 @@ def test_conv_pw_fused_equals_the_two_launches(n, h, pad, dil, dtype, form, rs):
     torch.cuda.synchronize()
     assert torch.all(y[M:] == 5.0)                                   # nothing written past the last pixel
     # the two launches
-    t2 = torch.empty(n, h, h, cm, dtype=dtype, device=DEV)
+    t2 = g_empty(n, h, h, cm, dtype=dtype)
     d2 = hip.conv_desc(t1d.data_ptr(), w2d.data_ptr(), b2d.data_ptr(), t2.data_ptr(), N=n, H=h, W=h, Cin=cin, OH=h, OW=h, Cout=cm, KH=3, KW=3,
                        pad=(pad, pad), dil=(dil, dil), act=1, tile=32)
     hip.check(hip.lib().usot_conv2d_lp(hip.stream(), C.byref(d2), dt, 0), 'conv2')
-    y2 = torch.empty(M, co, dtype=dtype, device=DEV)
+    y2 = g_empty(M, co, dtype=dtype)
     hip.check(hip.lib().usot_pw_panel_lp(hip.stream(), hip.ptr(t2), hip.ptr(w3d), hip.ptr(b3d), hip.ptr(resd), hip.ptr(y2), M, cm, co, 1, dt),
               'conv3')
     torch.cuda.synchronize()
@@ -1366,22 +1396,22 @@ def test_conv_pw_layer2_forms_equal_the_unfused_launches(n, h, stride, pad, cn, 
     dt = 1 if dtype == torch.float16 else 0
     t1d, w2d, w3d, w1d, b2d, b3d, b1d, resd = (a.to(DEV) for a in (t1, w2, w3, w1, b2, b3, b1, res))
     geo = dict(N=n, H=h, W=h, Cin=cm, OH=oh, OW=oh, Cout=cm, KH=3, KW=3, stride=stride, pad=(pad, pad), act=1)
-    y = torch.full((M + 2, co), 5.0, dtype=dtype, device=DEV)
-    t = torch.full((M + 2, max(cn, 64)), 5.0, dtype=dtype, device=DEV)
+    y = g_full((M + 2, co), 5.0, dtype=dtype)
+    t = g_full((M + 2, max(cn, 64)), 5.0, dtype=dtype)
     d = hip.conv_desc(t1d.data_ptr(), w2d.data_ptr(), b2d.data_ptr(), None, tile=form | (0 if rs else 4), **geo)
     exact = not rs or stride != 1                      # the row-shared loop (stride 1 only) sums in another order
     ulp = 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
     close = lambda a, b: float(((a.float() - b.float()).abs() / b.float().abs().clamp_min(1.0)).max()) <= 4 * ulp
-    t2 = torch.empty(n, oh, oh, cm, dtype=dtype, device=DEV)
+    t2 = g_empty(n, oh, oh, cm, dtype=dtype)
     d2 = hip.conv_desc(t1d.data_ptr(), w2d.data_ptr(), b2d.data_ptr(), t2.data_ptr(), tile=37, **geo)
     hip.check(hip.lib().usot_conv2d_lp(hip.stream(), C.byref(d2), dt, 0), 'conv2')
-    y2 = torch.empty(M, co, dtype=dtype, device=DEV)
+    y2 = g_empty(M, co, dtype=dtype)
     if cn:
         assert hip.lib().usot_conv_pw_pair_supported(cm, co, cn) == 1 and hip.lib().usot_conv_pw_pair_supported(cm, co, 64) == 0
         pd = hip.pw_pair_desc(None, w3d.data_ptr(), b3d.data_ptr(), resd.data_ptr(), y.data_ptr(), w1d.data_ptr(), b1d.data_ptr(),
                               t.data_ptr(), M, cm, co, cn, 1)
         hip.check(hip.lib().usot_conv_pw_pair_lp(hip.stream(), C.byref(d), C.byref(pd), dt), 'usot_conv_pw_pair_lp')
-        tt = torch.empty(M, cn, dtype=dtype, device=DEV)
+        tt = g_empty(M, cn, dtype=dtype)
         pd2 = hip.pw_pair_desc(t2.data_ptr(), w3d.data_ptr(), b3d.data_ptr(), resd.data_ptr(), y2.data_ptr(), w1d.data_ptr(),
                                b1d.data_ptr(), tt.data_ptr(), M, cm, co, cn, 1)
         hip.check(hip.lib().usot_pw_panel_pair_lp(hip.stream(), C.byref(pd2), dt), 'usot_pw_panel_pair_lp')
@@ -1421,17 +1451,17 @@ def test_conv_pw_layer3_with_the_next_conv1_as_fifth_phase(n, h, pad, act2, cm, 
     t1d, w2d, w3d, w1d, b2d, b3d, b1d, resd = (a.to(DEV) for a in (t1, w2, w3, w1, b2, b3, b1, res))
     geo = dict(N=n, H=h, W=h, Cin=cm, OH=h, OW=h, Cout=cm, KH=3, KW=3, pad=(pad, pad), dil=(pad, pad), act=1)
     tile = form | (0 if rs else 4)
-    y = torch.full((M + 2, co), 5.0, dtype=dtype, device=DEV)
-    t = torch.full((M + 2, cn), 5.0, dtype=dtype, device=DEV)
+    y = g_full((M + 2, co), 5.0, dtype=dtype)
+    t = g_full((M + 2, cn), 5.0, dtype=dtype)
     d = hip.conv_desc(t1d.data_ptr(), w2d.data_ptr(), b2d.data_ptr(), None, tile=tile, **geo)
     assert hip.lib().usot_conv_pw_pair_supported(cm, co, cn) == 1
     pd = hip.pw_pair_desc(None, w3d.data_ptr(), b3d.data_ptr(), resd.data_ptr(), y.data_ptr(), w1d.data_ptr(), b1d.data_ptr(),
                           t.data_ptr(), M, cm, co, cn, act2)
     hip.check(hip.lib().usot_conv_pw_pair_lp(hip.stream(), C.byref(d), C.byref(pd), dt), 'usot_conv_pw_pair_lp')
     # the four-phase kernel with the same k-loop, then the tiled conv1 on ITS Y
-    y2 = torch.empty(M, co, dtype=dtype, device=DEV)
+    y2 = g_empty(M, co, dtype=dtype)
     hip.check(hip.lib().usot_conv_pw_lp(hip.stream(), C.byref(d), hip.ptr(w3d), hip.ptr(b3d), hip.ptr(resd), hip.ptr(y2), dt), 'usot_conv_pw_lp')
-    tt = torch.empty(M, cn, dtype=dtype, device=DEV)
+    tt = g_empty(M, cn, dtype=dtype)
     d1 = hip.conv_desc(y2.data_ptr(), w1d.data_ptr(), b1d.data_ptr(), tt.data_ptr(), N=1, H=M, W=1, Cin=co, OH=M, OW=1, Cout=cn, KH=1, KW=1,
                        act=act2, tile=32)
     hip.check(hip.lib().usot_conv2d_lp(hip.stream(), C.byref(d1), dt, 0), 'conv1')
@@ -1467,8 +1497,8 @@ def test_conv_pw_at_the_timed_size_is_deterministic_and_equal_to_the_unfused_cha
     assert hip.lib().usot_conv_pw_pixels(M) == 256
     runs = []
     for _ in range(8):
-        y = torch.zeros(M, co, dtype=dtype, device=DEV)
-        t = torch.zeros(M, cn, dtype=dtype, device=DEV)
+        y = g_zeros(M, co, dtype=dtype)
+        t = g_zeros(M, cn, dtype=dtype)
         pd = hip.pw_pair_desc(None, w3.data_ptr(), b3.data_ptr(), res.data_ptr(), y.data_ptr(), w1.data_ptr(), b1.data_ptr(), t.data_ptr(),
                               M, cm, co, cn, 1)
         hip.check(hip.lib().usot_conv_pw_pair_lp(hip.stream(), C.byref(d), C.byref(pd), dt), 'usot_conv_pw_pair_lp')
@@ -1477,12 +1507,12 @@ def test_conv_pw_at_the_timed_size_is_deterministic_and_equal_to_the_unfused_cha
     for y, t in runs[1:]:
         assert torch.equal(y, runs[0][0]) and torch.equal(t, runs[0][1])
     if not rs:
-        t2 = torch.empty(n, h, h, cm, dtype=dtype, device=DEV)
+        t2 = g_empty(n, h, h, cm, dtype=dtype)
         d2 = hip.conv_desc(t1.data_ptr(), w2.data_ptr(), b2.data_ptr(), t2.data_ptr(), tile=32, **geo)
         hip.check(hip.lib().usot_conv2d_lp(hip.stream(), C.byref(d2), dt, 0), 'conv2')
-        y2 = torch.empty(M, co, dtype=dtype, device=DEV)
+        y2 = g_empty(M, co, dtype=dtype)
         hip.check(hip.lib().usot_pw_panel_lp(hip.stream(), hip.ptr(t2), hip.ptr(w3), hip.ptr(b3), hip.ptr(res), hip.ptr(y2), M, cm, co, 1, dt), 'conv3')
-        tt = torch.empty(M, cn, dtype=dtype, device=DEV)
+        tt = g_empty(M, cn, dtype=dtype)
         d1 = hip.conv_desc(y2.data_ptr(), w1.data_ptr(), b1.data_ptr(), tt.data_ptr(), N=1, H=M, W=1, Cin=co, OH=M, OW=1, Cout=cn, KH=1, KW=1,
                            act=1, tile=32)
         hip.check(hip.lib().usot_conv2d_lp(hip.stream(), C.byref(d1), dt, 0), 'conv1')
@@ -1511,7 +1541,7 @@ def test_conv_pw_overlapped_form_matches_float64_and_its_own_conv1(n, h, dil, ac
     res = torch.randn(M, co, generator=g).to(dtype)
     t1d, w2d, w3d, w1d, b2d, b3d, b1d, resd = (a.to(DEV) for a in (t1, w2, w3, w1, b2, b3, b1, res))
     assert L.usot_conv_pw_ov_supported(cm, co, cn) == 1
-    ws = torch.zeros(int(L.usot_conv_pw_ov_ws_bytes(M)) // 4, dtype=torch.int32, device=DEV)
+    ws = g_zeros(int(L.usot_conv_pw_ov_ws_bytes(M)) // 4, dtype=torch.int32)
     d2 = hip.conv_desc(t1d.data_ptr(), w2d.data_ptr(), b2d.data_ptr(), None, N=n, H=h, W=h, Cin=cm, OH=h, OW=h, Cout=cm, KH=3, KW=3,
                        pad=(dil, dil), dil=(dil, dil), act=1)
     x64 = t1.double().permute(0, 3, 1, 2)
@@ -1520,8 +1550,8 @@ def test_conv_pw_overlapped_form_matches_float64_and_its_own_conv1(n, h, dil, ac
     ref = (t2r @ w3.double().t() + b3.double() + res.double()).relu()
     ulp = 2.0 ** -8
     for _ in range(2):
-        y = torch.full((M + 2, co), 5.0, dtype=dtype, device=DEV)
-        t = torch.full((M + 2, cn), 5.0, dtype=dtype, device=DEV)
+        y = g_full((M + 2, co), 5.0, dtype=dtype)
+        t = g_full((M + 2, cn), 5.0, dtype=dtype)
         pd = hip.pw_pair_desc(None, w3d.data_ptr(), b3d.data_ptr(), resd.data_ptr(), y.data_ptr(), w1d.data_ptr(), b1d.data_ptr(),
                               t.data_ptr(), M, cm, co, cn, act2)
         hip.check(L.usot_conv_pw_ov_lp(hip.stream(), C.byref(d2), C.byref(pd), dt, hip.ptr(ws)), 'usot_conv_pw_ov_lp')
@@ -1529,7 +1559,7 @@ def test_conv_pw_overlapped_form_matches_float64_and_its_own_conv1(n, h, dil, ac
         assert torch.all(y[M:] == 5.0) and torch.all(t[M:] == 5.0)
         assert int(ws[:2 * ((M + 127) // 128) + 1].abs().sum()) == 0
         assert float(((y[:M].float().cpu().double() - ref).abs() / ref.abs().clamp_min(1.0)).max()) <= 4 * ulp
-        tt = torch.empty(M, cn, dtype=dtype, device=DEV)
+        tt = g_empty(M, cn, dtype=dtype)
         yc = y[:M].contiguous()
         d1 = hip.conv_desc(yc.data_ptr(), w1d.data_ptr(), b1d.data_ptr(), tt.data_ptr(), N=1, H=M, W=1, Cin=co, OH=M, OW=1, Cout=cn, KH=1, KW=1,
                            act=act2, tile=32)
@@ -1575,7 +1605,7 @@ def test_bw_probe_kernels_move_the_right_bytes():
     adjacent 1 KiB rows of each 64-element group, bad arguments are refused."""
     n = 1 << 20
     src = torch.randn(n // 4, device=DEV)
-    dst = torch.zeros(n // 4, device=DEV)
+    dst = g_zeros(n // 4)
     L = hip.lib()
     hip.check(L.usot_bw_probe(hip.stream(), hip.ptr(src), hip.ptr(dst), n, 1), 'copy')
     assert torch.equal(dst, src)
@@ -1595,7 +1625,7 @@ def test_bw_probe_kernels_move_the_right_bytes():
     # mode 3, GroupDW's traffic pattern: S samples = three 29 x 29 x 256 maps read, one 25 x 25 x 256 map written, nothing beyond
     S = 3
     src3 = torch.ones(3 * S * 841 * 256, device=DEV)
-    dst3 = torch.zeros(S * 625 * 256 + 1024, device=DEV)
+    dst3 = g_zeros(S * 625 * 256 + 1024)
     hip.check(L.usot_bw_probe(hip.stream(), hip.ptr(src3), hip.ptr(dst3), 3 * S * 841 * 1024, 3), 'groupdw pattern')
     torch.cuda.synchronize()
     assert float(dst3[:S * 625 * 256].min()) > 0.0 and float(dst3[S * 625 * 256:].abs().max()) == 0.0
@@ -1629,7 +1659,7 @@ def test_conv_kstream_lp(N, H, W, Cin, Cout, stride, pad, dil, act, dtype):
         ref = ref.relu()
     xd, wd, bd = x.to(DEV), w.reshape(Cout, 9 * Cin).contiguous().to(DEV), b.to(DEV)
     M = N * OH * OW
-    y = torch.full((M + 2, Cout), 5.0, dtype=dtype, device=DEV)
+    y = g_full((M + 2, Cout), 5.0, dtype=dtype)
     dt = 1 if dtype == torch.float16 else 0
     hip.check(L.usot_conv_kstream_lp(hip.stream(), hip.ptr(xd), hip.ptr(wd), hip.ptr(bd), hip.ptr(y), N, H, W, Cin, Cout, stride, pad, dil,
                                      act, dt), 'conv_kstream')
@@ -1637,7 +1667,7 @@ def test_conv_kstream_lp(N, H, W, Cin, Cout, stride, pad, dil, act, dtype):
     got = y[:M].reshape(N, OH, OW, Cout).float()
     tol = 2 ** -8 if dtype == torch.bfloat16 else 2 ** -11
     assert float(((got.cpu().double() - ref).abs() / ref.abs().clamp_min(1.0)).max()) <= tol * 1.01
-    y2 = torch.empty(N, OH, OW, Cout, dtype=dtype, device=DEV)
+    y2 = g_empty(N, OH, OW, Cout, dtype=dtype)
     d = hip.conv_desc(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), y2.data_ptr(), N=N, H=H, W=W, Cin=Cin, OH=OH, OW=OW, Cout=Cout,
                       KH=3, KW=3, stride=stride, pad=(pad, pad), dil=(dil, dil), act=act, tile=13)
     hip.check(L.usot_conv2d_lp(hip.stream(), Ct.byref(d), dt, 0), 'tiled')
@@ -1659,7 +1689,7 @@ def test_pw_kstream_lp_reducing_conv(M, act, bias, dtype):
     x = torch.randn(M, K, generator=g).to(dtype).to(DEV)
     w = (torch.randn(N, K, generator=g) / 32).to(dtype).to(DEV)
     b = torch.randn(N, generator=g).to(DEV) if bias else None
-    y = torch.full((M + 8, N), 7.0, dtype=dtype, device=DEV)
+    y = g_full((M + 8, N), 7.0, dtype=dtype)
     hip.check(hip.lib().usot_pw_kstream_lp(hip.stream(), hip.ptr(x), hip.ptr(w), hip.ptr(b) if bias else None, hip.ptr(y), M, K, N,
                                            act, 1 if dtype == torch.float16 else 0), 'usot_pw_kstream_lp')
     ref = x.float() @ w.float().t() + (b if bias else 0.0)
@@ -1689,7 +1719,7 @@ def test_conv3x3_halo_lp(N, H, W, act, dtype):
     if act:
         ref = ref.relu()
     xd, wd, bd = x.to(DEV), w.reshape(64, 576).contiguous().to(DEV), b.to(DEV)
-    y = torch.full((N * H * W + 2, 64), 5.0, dtype=dtype, device=DEV)
+    y = g_full((N * H * W + 2, 64), 5.0, dtype=dtype)
     dt = 1 if dtype == torch.float16 else 0
     assert hip.lib().usot_conv3x3_halo_supported(64, 64) == 1 and hip.lib().usot_conv3x3_halo_supported(128, 128) == 0
     hip.check(hip.lib().usot_conv3x3_halo_lp(hip.stream(), hip.ptr(xd), hip.ptr(wd), hip.ptr(bd), hip.ptr(y), N, H, W, 64, 64, act, dt), 'halo')
@@ -1697,7 +1727,7 @@ def test_conv3x3_halo_lp(N, H, W, act, dtype):
     got = y[:N * H * W].reshape(N, H, W, 64)
     tol = 2 ** -8 if dtype == torch.bfloat16 else 2 ** -11
     assert float(((got.float().cpu().double() - ref).abs() / ref.abs().clamp_min(1.0)).max()) <= tol * 1.01
-    y2 = torch.empty(N, H, W, 64, dtype=dtype, device=DEV)
+    y2 = g_empty(N, H, W, 64, dtype=dtype)
     d = hip.conv_desc(xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), y2.data_ptr(), N=N, H=H, W=W, Cin=64, OH=H, OW=W, Cout=64, KH=3, KW=3,
                       pad=(1, 1), act=act, tile=13)
     hip.check(hip.lib().usot_conv2d_lp(hip.stream(), C.byref(d), dt, 0), 'tiled')
@@ -1733,8 +1763,8 @@ def test_bneck_first_lp(N, H, W, dtype):
     xd, w1d, w2d, w3cd, wnd = dev(x), dev(w1), dev(w2.reshape(64, 576)), dev(torch.cat([w3, wd], 1)), dev(wn)
     b1d, b2d, b3d, bnd = dev(b1), dev(b2), dev(b3c), dev(bn)
     M = N * H * W
-    y = torch.full((M + 1, 256), 5.0, dtype=dtype, device=DEV)
-    t = torch.full((M + 1, 64), 7.0, dtype=dtype, device=DEV)
+    y = g_full((M + 1, 256), 5.0, dtype=dtype)
+    t = g_full((M + 1, 64), 7.0, dtype=dtype)
     dt = 1 if dtype == torch.float16 else 0
     assert hip.lib().usot_bneck_first_supported(64, 64, 256, 64) == 1 and hip.lib().usot_bneck_first_supported(256, 64, 256, 64) == 0
     d = hip.bneck_desc(*[hip.ptr(v) for v in (xd, w1d, b1d, w2d, b2d, w3cd, b3d, wnd, bnd, y, t)], N, H, W)
@@ -1776,8 +1806,8 @@ def test_bneck_tail_lp(N, H, W, cn, dtype):
     dev = lambda v: v.contiguous().to(DEV)
     t1d, resd, w2d, w3d, wnd, b2d, b3d, bnd = dev(t1), dev(res), dev(w2.reshape(64, 576)), dev(w3), dev(wn), dev(b2), dev(b3), dev(bn)
     M = N * H * W
-    y = torch.full((M + 1, 256), 5.0, dtype=dtype, device=DEV)
-    t = torch.full((M + 1, cn), 7.0, dtype=dtype, device=DEV)
+    y = g_full((M + 1, 256), 5.0, dtype=dtype)
+    t = g_full((M + 1, cn), 7.0, dtype=dtype)
     dt = 1 if dtype == torch.float16 else 0
     assert hip.lib().usot_bneck_tail_supported(64, 256, cn) == 1 and hip.lib().usot_bneck_tail_supported(64, 256, 256) == 0
     d = hip.bneck_desc(hip.ptr(t1d), hip.ptr(resd), None, hip.ptr(w2d), hip.ptr(b2d), hip.ptr(w3d), hip.ptr(b3d), hip.ptr(wnd), hip.ptr(bnd),
@@ -1840,7 +1870,7 @@ def test_groupdw_and_conf_reduce_low_precision_outputs(ow, dtype):
     zs = [torch.randn(S, hk, wk, 256, generator=g).to(DEV) for hk, wk in geo]
     w = np.array([0.2, 0.3, 0.5], np.float32)
     ref = hip.groupdw(xs, zs, w, x_rep=rep, cols=6)
-    out = torch.full((S * ow * ow * 256 + 8,), 3.0, dtype=dtype, device=DEV)
+    out = g_full((S * ow * ow * 256 + 8,), 3.0, dtype=dtype)
     d = hip.groupdw_desc([t.data_ptr() for t in xs], [t.data_ptr() for t in zs], out.data_ptr(), w, S=S, x_rep=rep, OH=ow, OW=ow, Cc=256,
                          x_cs=[256] * 3, x_co=[0] * 3, z_cs=[256] * 3, z_co=[0] * 3)
     dt = 1 if dtype == torch.float16 else 2
@@ -1851,7 +1881,7 @@ def test_groupdw_and_conf_reduce_low_precision_outputs(ow, dtype):
     B, M, P = 3, 7, ow * ow
     cv = torch.rand(B * M, ow, ow, 512, generator=g).to(DEV) + 0.1
     r32 = hip.conf_fusion_reduce(cv, B, M)
-    o = torch.full((B * P * 256 + 8,), 3.0, dtype=dtype, device=DEV)
+    o = g_full((B * P * 256 + 8,), 3.0, dtype=dtype)
     hip.check(hip.lib().usot_conf_fusion_reduce_lp(hip.stream(), hip.ptr(cv), 0, hip.ptr(o), B, M, P, 256, dt), 'conf_reduce_lp')
     torch.cuda.synchronize()
     assert same_up_to_ties(o[:-8].reshape(r32.shape), r32) and torch.all(o[-8:] == 3.0)

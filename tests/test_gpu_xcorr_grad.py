@@ -13,15 +13,28 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import guarded  # noqa: E402
 import usot_oracle as orc  # noqa: E402
-from usot_amd import hip  # noqa: E402
+from usot_amd import autograd as hip_autograd, hip  # noqa: E402
 
 DEV = 'cuda:0'
 BAR = 1e-5
 GEO = ((5, 5), (3, 5), (5, 3))                    # GroupDW's three templates
 HEAD = [(29, 29, 5, 5), (27, 29, 3, 5), (29, 27, 5, 3)]
 XC = HEAD + [(31, 31, 5, 5), (33, 31, 5, 3), (12, 9, 4, 2), (64, 64, 5, 5), (70, 70, 5, 5), (7, 7, 7, 7), (31, 31, 7, 7)]
+# dispatch edges of the plane kernels: Wx 32 | 33 (two planes per wavefront | one), Wx 64 | 65 (specialised | generic), OH = 1 and
+# OW = 1 on the specialised templates, a single output
+XC_EDGES = [(9, 32, 5, 5), (9, 33, 5, 5), (9, 64, 5, 3), (9, 65, 5, 3), (5, 29, 5, 5), (29, 5, 5, 5), (3, 5, 3, 5)]
+XC = XC + XC_EDGES
 CASES = [(s, p) for s in XC for p in ((1, 1), (2, 24), (3, 257))] + [(s, (12, 256)) for s in HEAD]
+
+
+@pytest.fixture(autouse=True)
+def _memory_guard():
+    """Every output a wrapper of usot_amd.hip / usot_amd.autograd allocates starts as NaN and sits between canaries
+    (tests/guarded.py); the guards are checked when the test ends."""
+    with guarded.patched(hip, hip_autograd):
+        yield
 
 
 def rel_err(got, ref):
@@ -45,10 +58,11 @@ def ref_grads(x, k, dout):
 
 
 def raw_grads(x, k, dout, scale=1.0):
-    """The two C entry points on NaN-filled outputs (an element nobody wrote stays NaN).  Device tensors in and out."""
+    """The two C entry points on NaN-filled outputs between canaries (an element nobody wrote stays NaN).  Device tensors in
+    and out."""
     (b, c, hx, wx), (hk, wk) = x.shape, k.shape[2:]
-    dx = torch.full_like(x, float('nan'))
-    dk = torch.full_like(k, float('nan'))
+    dx = guarded.alloc(x.shape, x.dtype, x.device)
+    dk = guarded.alloc(k.shape, k.dtype, k.device)
     L = hip.lib()
     hip.check(L.usot_xcorr_depthwise_bwd_x_f32(hip.stream(), hip.ptr(dout), hip.ptr(k), hip.ptr(dx), b * c, hx, wx, hk, wk,
                                                C.c_float(scale)), 'usot_xcorr_depthwise_bwd_x_f32')
