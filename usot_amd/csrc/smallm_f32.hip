@@ -27,6 +27,11 @@
 // ds_read_b128 trick (a lane reads 4 consecutive k and issues 4 MFMAs; quad q owns k-slot q).  Both filter banks are
 // pre-packed in FRAGMENT order (one contiguous KiB per 16 channels x 16 k, see usot_pw_pair_f32 in usot_hip.h) and
 // stream straight from L2 into a ring of eight register fragments per wave; only the pixel tile and Y go through LDS.
+// The ring is PINNED (USOT_RING_PIN below): a round reads the next round's B fragment from LDS, issues the refill of its own slot,
+// then its MFMAs, which therefore wait on vmcnt(USOT_RING) - eight loads in flight - and on no LDS read.  The streams start before
+// the barriers that do not concern them: W3's first fragments, the residual and the bias before the pixel tile is staged, W1's first
+// fragments before the barrier that publishes Y (PairHead, pair_tail).  tests/test_smallm_ring_schedule.py reads the waits in the
+// assembly; -DUSOT_RING_UNPINNED builds the schedule hipcc chooses on its own (refills sunk to their uses: 1-3 loads in flight).
 // When GEMM2 has fewer column blocks than waves its k range is split over wave groups, meeting in LDS (fixed order).
 //
 // S > 1 — few pixel tiles (M = 961: 61): S workgroups share a pixel tile, each owning CO / S channels of Y: GEMM1 for its
@@ -41,6 +46,17 @@
 
 #ifndef USOT_RING          // filter fragments (1 KiB per wave each) a wave keeps in flight
 #define USOT_RING 8
+#endif
+// The ring exists in the BUILT code only while the issue order below is pinned: left alone, hipcc's scheduler sinks every refill
+// down to its use, a round's MFMAs then wait on vmcnt(0..2) and the ring is one to three loads deep (scripts/ring_depth.py prints
+// the waits; docs/LAB_NOTEBOOK.md A.5).  -DUSOT_RING_UNPINNED compiles the file without the pins and without the hoisted
+// prefetches (the schedule before they existed): the A/B partner of tests/test_gpu_smallm_ring.py and of the timings.
+#ifdef USOT_RING_UNPINNED
+#define USOT_RING_PIN() ((void)0)
+static constexpr bool kPinned = false;
+#else
+#define USOT_RING_PIN() __builtin_amdgcn_sched_barrier(0)
+static constexpr bool kPinned = true;
 #endif
 
 namespace {
@@ -85,6 +101,7 @@ struct GemmRing {
     {
 #pragma unroll
         for (int n = 0; n < PF; ++n) ring[n] = frag(wf, cb0, r0, n);
+        USOT_RING_PIN();                                  // the loads are issued HERE, not where the first MFMA wants them
     }
     __device__ __forceinline__ void run(const f32x4 *__restrict__ wf, const float *bs, int cb0, int r0, f32x4 (&acc)[CBW])
     {
@@ -99,13 +116,19 @@ struct GemmRing {
         for (int u = 0; u < CBW; ++u) { part[u][0] = part[u][1] = zero; tot[u].clear(); }
         if constexpr (BLO > 0) {
             auto h = [](const f32x4 &v) { return __builtin_bit_cast(f16x8_t, v); };
+            // pinned: the B fragments of step n + 2 are read while step n's MFMAs run, the refills are issued in front of them
+            auto bfrag = [&](int n, int lo) { return *(const f32x4 *)(bs + lo + ((r0 + n % RS) >> 1) * 16); };
+            f32x4 bhn, bln;
+            if (kPinned) { bhn = bfrag(0, 0); bln = bfrag(0, BLO); }
 #pragma unroll
             for (int n = 0; n < N; n += 2) {
-                const int step = (r0 + n % RS) >> 1;
-                const f32x4 bh = *(const f32x4 *)(bs + step * 16), bl = *(const f32x4 *)(bs + BLO + step * 16);
+                const f32x4 bh = kPinned ? bhn : bfrag(n, 0), bl = kPinned ? bln : bfrag(n, BLO);
+                if (kPinned && n + 2 < N) { bhn = bfrag(n + 2, 0); bln = bfrag(n + 2, BLO); }
                 const f32x4 ah = ring[n % PF], al = ring[(n + 1) % PF];
+                USOT_RING_PIN();
                 if (n + PF < N) ring[n % PF] = frag(wf, cb0, r0, n + PF);
                 if (n + 1 + PF < N) ring[(n + 1) % PF] = frag(wf, cb0, r0, n + 1 + PF);
+                USOT_RING_PIN();
                 const int u = n / RS, rr = n % RS, g = rr / G, s = g & 1;
                 const bool first = rr % G == 0;
                 if (first && g >= 2) tot[u].add(part[u][s]);
@@ -114,11 +137,19 @@ struct GemmRing {
                 part[u][s] = __builtin_amdgcn_mfma_f32_16x16x32_f16(h(ah), h(bh), part[u][s], 0, 0, 0);
             }
         } else {
+        // pinned: per round, B of the NEXT round is read from LDS, then the refill of this round's slot is issued, then the four
+        // MFMAs: they wait for neither the LDS read (a round old) nor the refills (PF loads behind this round's fragment)
+        auto bfrag = [&](int n) { return *(const f32x4 *)(bs + (r0 + n % RS) * 16); };
+        f32x4 bn;
+        if (kPinned) bn = bfrag(0);
 #pragma unroll
         for (int n = 0; n < N; ++n) {
-            const f32x4 b = *(const f32x4 *)(bs + (r0 + n % RS) * 16);
+            const f32x4 b = kPinned ? bn : bfrag(n);
+            if (kPinned && n + 1 < N) bn = bfrag(n + 1);
             const f32x4 a = ring[n % PF];
+            USOT_RING_PIN();
             if (n + PF < N) ring[n % PF] = frag(wf, cb0, r0, n + PF);
+            USOT_RING_PIN();
             const int u = n / RS, rr = n % RS, g = rr / G, s = g & 1;
             const bool first = rr % G == 0;
             if (first && g >= 2) tot[u].add(part[u][s]);
@@ -137,10 +168,14 @@ struct GemmRing {
     }
 };
 
+// the ring of a GEMM at the file's depth (or the GEMM's whole fragment count when that is less)
+template <int CBW, int RS, int RT, int BLO = 0, int PFD = USOT_RING>
+using RingOf = GemmRing<CBW, RS, RT, (CBW * RS < PFD ? CBW * RS : PFD), BLO>;
+
 template <int CBW, int RS, int RT, int BLO = 0>
 __device__ __forceinline__ void gemm_blocks(const f32x4 *__restrict__ wf, const float *bs, int cb0, int r0, f32x4 (&acc)[CBW])
 {
-    GemmRing<CBW, RS, RT, (CBW * RS < USOT_RING ? CBW * RS : USOT_RING), BLO> g;
+    RingOf<CBW, RS, RT, BLO> g;
     g.prefetch(wf, cb0, r0);
     g.run(wf, bs, cb0, r0, acc);
 }
@@ -173,8 +208,41 @@ __device__ __forceinline__ void note_not_finite(int *ovf, const f32x4 &a)
 // meeting) -> T.  Xs: the [16][CM + 4] tile (published by a barrier before the call); Ys / Ps: scratch.
 // H16: split-fp16 operands (GemmRing, BLO > 0): both banks pre-split with their per-row factors 1 / (row scale x 8) appended
 // (w3p[COT CM ..], w1p[CN COT ..]: hip.pw_pair_s16_pack), the pixel tile staged split by the caller, the Y tile split here.
+// What GEMM1 of a pair needs that does not depend on the pixel tile: W3's first fragments, the residual, the bias (and the
+// split-fp16 row factors).  issue() goes in front of the staging of the pixel tile and its barrier: the kernels call it there.
+// The USOT_RING_UNPINNED build does not use it: pair_tail then loads all of this itself, after that barrier.
+template <int CM, int COT, int S, bool H16>
+struct PairHead {
+    static constexpr int NW = 8, BM = 16, CO = COT / S, R1 = CM / 16, NB1 = CO / 16, CBW1 = NB1 / NW;
+    RingOf<CBW1, R1, R1, H16 ? CM / 2 : 0> g;
+    f32x4 rr[CBW1], bb[CBW1], sc[H16 ? CBW1 : 1];
+    __device__ __forceinline__ const f32x4 *wf(const PwF &p, int sl) const
+    {
+        return (const f32x4 *)p.w3p + (threadIdx.x & 63) + (long)sl * NB1 * R1 * 64;
+    }
+    __device__ __forceinline__ void issue(const PwF &p, int pt, int sl)
+    {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, quad = lane >> 4;
+        const int m = pt * BM + (lane & 15);
+        const bool mok = m < p.M;
+        g.prefetch(wf(p, sl), wave * CBW1, 0);            // the stream first: nothing it waits for is behind a cold load
+#pragma unroll
+        for (int u = 0; u < CBW1; ++u) {
+            const int cog = sl * CO + (wave * CBW1 + u) * 16 + quad * 4;
+            if constexpr (H16) sc[u] = *(const f32x4 *)(p.w3p + (long)COT * CM + cog);
+            rr[u] = mok ? *(const f32x4 *)(p.res + (long)m * COT + cog) : f32x4{0.f, 0.f, 0.f, 0.f};
+            if (p.rparts > 1 && mok) {       // deferred split-K reduction of the shortcut convolution: parts in order, then its bias
+                for (int q = 1; q < p.rparts; ++q) rr[u] += *(const f32x4 *)(p.res + ((long)q * p.M + m) * COT + cog);
+                rr[u] += *(const f32x4 *)(p.rbias + cog);
+            }
+            bb[u] = *(const f32x4 *)(p.b3 + cog);
+        }
+        USOT_RING_PIN();
+    }
+};
+
 template <int CM, int COT, int CN, int S, bool H16 = false>
-__device__ __forceinline__ void pair_tail(const PwF &p, const float *Xs, float *Ys, float *Ps, int pt, int sl)
+__device__ __forceinline__ void pair_tail(const PwF &p, PairHead<CM, COT, S, H16> &hd, const float *Xs, float *Ys, float *Ps, int pt, int sl)
 {
     constexpr int NW = 8, BM = 16;
     constexpr int CO = COT / S;                           // channels of Y this workgroup owns
@@ -192,15 +260,25 @@ __device__ __forceinline__ void pair_tail(const PwF &p, const float *Xs, float *
     const int m = pt * BM + l15;
     const bool mok = m < p.M;
 
+    // GEMM2's ring: wave -> (column blocks, k-slice).  Its first fragments of W1 depend on nothing the Y barrier protects: they
+    // are issued as soon as GEMM1's ring is drained, and fly under GEMM1's epilogue and that barrier
+#ifndef USOT_RING_UNPINNED
+    const int ksl = KS > 1 ? wave / NB2 : 0;
+    const int cb0 = KS > 1 ? wave % NB2 : wave * CBW2;
+    const f32x4 *wf2 = (const f32x4 *)p.w1p + lane + (long)sl * R2 * 64;
+    RingOf<CBW2, RS2, R2T, H16 ? CO / 2 : 0> g2;
+#endif
+
     // ---- GEMM1: K = CM from the pixel tile; this wave's CBW1 column blocks of the slice (residual and bias fly under it)
     {
+#ifdef USOT_RING_UNPINNED
         f32x4 rr[CBW1], bb[CBW1], sc[H16 ? CBW1 : 1];
 #pragma unroll
         for (int u = 0; u < CBW1; ++u) {
             const int cog = sl * CO + (wave * CBW1 + u) * 16 + quad * 4;
             if constexpr (H16) sc[u] = *(const f32x4 *)(p.w3p + (long)COT * CM + cog);
             rr[u] = mok ? *(const f32x4 *)(p.res + (long)m * COT + cog) : f32x4{0.f, 0.f, 0.f, 0.f};
-            if (p.rparts > 1 && mok) {       // deferred split-K reduction of the shortcut convolution: parts in order, then its bias
+            if (p.rparts > 1 && mok) {
                 for (int q = 1; q < p.rparts; ++q) rr[u] += *(const f32x4 *)(p.res + ((long)q * p.M + m) * COT + cog);
                 rr[u] += *(const f32x4 *)(p.rbias + cog);
             }
@@ -208,6 +286,14 @@ __device__ __forceinline__ void pair_tail(const PwF &p, const float *Xs, float *
         }
         f32x4 acc[CBW1];
         gemm_blocks<CBW1, R1, R1, H16 ? CM / 2 : 0>((const f32x4 *)p.w3p + lane + (long)sl * NB1 * R1 * 64, Xs + l15 * XP + quad * 4, wave * CBW1, 0, acc);
+#else
+        const auto &rr = hd.rr;
+        const auto &bb = hd.bb;
+        const auto &sc = hd.sc;
+        f32x4 acc[CBW1];
+        hd.g.run(hd.wf(p, sl), Xs + l15 * XP + quad * 4, wave * CBW1, 0, acc);
+        g2.prefetch(wf2, cb0, ksl * RS2);
+#endif
 #pragma unroll
         for (int u = 0; u < CBW1; ++u) {
             const int co = (wave * CBW1 + u) * 16 + quad * 4;              // within the slice
@@ -225,11 +311,15 @@ __device__ __forceinline__ void pair_tail(const PwF &p, const float *Xs, float *
     }
     __syncthreads();                                      // Y tile (slice) complete
 
-    // ---- GEMM2: K = CO from LDS; wave -> (column blocks, k-slice)
+    // ---- GEMM2: K = CO from LDS
+    f32x4 acc[CBW2];
+#ifdef USOT_RING_UNPINNED
     const int ksl = KS > 1 ? wave / NB2 : 0;
     const int cb0 = KS > 1 ? wave % NB2 : wave * CBW2;
-    f32x4 acc[CBW2];
     gemm_blocks<CBW2, RS2, R2T, H16 ? CO / 2 : 0>((const f32x4 *)p.w1p + lane + (long)sl * R2 * 64, Ys + l15 * YP + quad * 4, cb0, ksl * RS2, acc);
+#else
+    g2.run(wf2, Ys + l15 * YP + quad * 4, cb0, ksl * RS2, acc);
+#endif
     if constexpr (H16) {                                  // unscaled partial sums from here on (exact: powers of two)
 #pragma unroll
         for (int u = 0; u < CBW2; ++u) {
@@ -298,6 +388,8 @@ __global__ __launch_bounds__(512) void pw_pair_f32_kernel(const PwF p)
     const int tid = threadIdx.x;
     const int pt = S > 1 ? (int)blockIdx.x / S : (int)blockIdx.x, sl = S > 1 ? (int)blockIdx.x % S : 0;
     const int bm0 = pt * BM;
+    PairHead<CM, COT, S, H16> hd;
+    if (kPinned) hd.issue(p, pt, sl);                     // W3's stream, residual and bias start before the cold pixel tile
     // pixel tile -> LDS (rows past M are zero)
     if (p.parts > 1) {
         // deferred split-K reduction of the producing convolution: the partial tiles are summed HERE, in part order, bias and
@@ -328,7 +420,7 @@ __global__ __launch_bounds__(512) void pw_pair_f32_kernel(const PwF p)
         }
     }
     __syncthreads();
-    pair_tail<CM, COT, CN, S, H16>(p, Xs, Ys, Ps, pt, sl);
+    pair_tail<CM, COT, CN, S, H16>(p, hd, Xs, Ys, Ps, pt, sl);
 }
 
 // ---- a whole bottleneck tail in one launch (layer1 at batch 1): conv2 (3x3 / stride 1, CIN -> CM) + BN + ReLU, then the
@@ -361,7 +453,7 @@ __global__ __launch_bounds__(512) void pw_triple_f32_kernel(const PwT q)
     const int pt = blockIdx.x, bm0 = pt * BM;
     const int cb = wave % NB0, ksl = wave / NB0;
     const f32x4 *wf = (const f32x4 *)q.w2p + lane;
-    GemmRing<1, RS0, RT0, (RS0 < USOT_RING ? RS0 : USOT_RING)> g;
+    RingOf<1, RS0, RT0> g;
     g.prefetch(wf, cb, ksl * RS0);
     if (tid < BM) {
         const int mm = bm0 + tid;
@@ -389,6 +481,8 @@ __global__ __launch_bounds__(512) void pw_triple_f32_kernel(const PwT q)
     __syncthreads();
     f32x4 acc[1];
     g.run(wf, X0 + l15 * XP0 + quad * 4, cb, ksl * RS0, acc);
+    PairHead<CM, COT, 1, false> hd;
+    if (kPinned) hd.issue(p, pt, 0);                      // the pair's stream starts before the barriers that publish conv2's tile
     if constexpr (KS0 > 1) {
         if (ksl > 0) *(f32x4 *)(Ps + ((ksl - 1) * BM + l15) * (CM + 4) + cb * 16 + quad * 4) = acc[0];
         __syncthreads();
@@ -404,7 +498,7 @@ __global__ __launch_bounds__(512) void pw_triple_f32_kernel(const PwT q)
         *(f32x4 *)(Xs + l15 * XP + cb * 16 + quad * 4) = v;           // rows past M hold relu(b2): never stored
     }
     __syncthreads();                                      // conv2's tile complete (and Ps free again)
-    pair_tail<CM, COT, CN, 1>(p, Xs, Ys, Ps, pt, 0);
+    pair_tail<CM, COT, CN, 1>(p, hd, Xs, Ys, Ps, pt, 0);
 }
 
 template <int CM, int CO, int CN, int S = 1, bool H16 = false> int launch(hipStream_t s, const PwF &p)
@@ -470,7 +564,7 @@ __global__ __launch_bounds__(512) void pw_single_f32_kernel(const Pw1 p)
     const int ksl = KS > 1 ? wave / NB : 0;
     const int cb0 = KS > 1 ? wave % NB : wave * CBW;      // within the slice
     const f32x4 *wf = (const f32x4 *)p.wp + lane + (long)sl * NB * RT * 64;
-    GemmRing<CBW, RS, RT, (CBW * RS < PFD ? CBW * RS : PFD)> g;
+    RingOf<CBW, RS, RT, 0, PFD> g;
     g.prefetch(wf, cb0, ksl * RS);                        // the filter stream starts before the pixel tile arrives
     for (int i = tid; i < BM * (K / 4); i += NW * 64) {
         const int row = i / (K / 4), c4 = i - row * (K / 4);
@@ -555,7 +649,7 @@ __global__ __launch_bounds__(512) void stream_conv3x3_f32_kernel(const PwC p)
     const int ksl = KS > 1 ? wave / NB : 0;
     const int cb0 = KS > 1 ? wave % NB : wave * CBW;
     const f32x4 *wf = (const f32x4 *)p.wp + lane + (long)sl * NB * RT * 64;
-    GemmRing<CBW, RS, RT, (CBW * RS < USOT_RING ? CBW * RS : USOT_RING)> g;
+    RingOf<CBW, RS, RT> g;
     g.prefetch(wf, cb0, ksl * RS);
     if (tid < BM) {
         const int mm = bm0 + tid;
