@@ -2,7 +2,9 @@
 """Every output of the small-M fp32 kernels (csrc/smallm_f32.hip) on seeded inputs, for the library given by USOT_HIP_LIB, written
 as one torch file {case: [tensors]}: the default build (pinned ring, hoisted prefetches) and the -DUSOT_RING_UNPINNED build must
 write the same BITS (tests/test_gpu_smallm_ring.py).  The smallest shapes that reach every path: M = 17 = one full and one ragged
-16-pixel tile; the sliced forms run twice on one workspace, so a ticket that was not reset shows.
+16-pixel tile, M = 16 = an exact tile, M = 31 = a 15-row tail; 5 x 5 and 4 x 4 maps (M = 25, 16); the sliced forms run twice on
+one workspace, so a ticket that was not reset shows.  A case name carries its size (_m16, _m31, _4x4); the names without one are
+M = 17 and the 5 x 5 map.
     python scripts/smallm_bits.py OUT.pt"""
 import ctypes as C, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -10,7 +12,8 @@ sys.path.insert(0, ROOT)
 import torch
 from usot_amd import hip
 DEV = 'cuda:0'
-M = 17
+MS = (17, 16, 31)
+MAPS = (5, 4)
 PAIRS_UNSLICED = [(64, 256, 64), (64, 256, 128), (128, 512, 256)]
 PAIRS_SLICED = [(128, 512, 128), (256, 1024, 256)]
 TRIPLES = [(64, 64, 256, 64), (64, 64, 256, 128), (128, 128, 512, 128)]
@@ -18,14 +21,33 @@ SINGLES = [(1024, 256), (256, 1024), (512, 128), (128, 512)]
 STREAMED = [(128, 128), (256, 256)]
 
 
+def m_tag(M):
+    return '' if M == 17 else '_m%d' % M
+
+
+def map_tag(hw):
+    return '' if hw == 5 else '_%dx%d' % (hw, hw)
+
+
+REPEATED = ('pair_sliced_128_512_128', 'pair_sliced_256_1024_256', 'pair_deferred_256_1024_256', 'pair_split16_256_1024_256')
+
+
+def repeated_cases():
+    """The cases launched twice on one workspace: [y0, t0, y1, t1, ...]."""
+    return [n + m_tag(M) for M in MS for n in REPEATED]
+
+
 def cases():
     """Names of everything main() writes, in order (the test's parametrisation)."""
-    out = ['pair_%d_%d_%d' % s for s in PAIRS_UNSLICED]
-    out += ['pair_sliced_%d_%d_%d' % s for s in PAIRS_SLICED]
-    out += ['pair_no_ws_128_512_128', 'pair_deferred_256_1024_256', 'pair_split16_256_1024_256']
-    out += ['triple_%d_%d_%d_%d_pd%d' % (s + (pd,)) for s in TRIPLES for pd in (1, 2)]
-    out += ['single_%d_%d_%s' % (s + (r,)) for s in SINGLES for r in ('plain', 'res')]
-    out += ['streamed_%d_%d_pd%d' % (s + (pd,)) for s in STREAMED for pd in (1, 2)]
+    out = []
+    for M in MS:
+        out += ['pair_%d_%d_%d' % s + m_tag(M) for s in PAIRS_UNSLICED]
+        out += ['pair_sliced_%d_%d_%d' % s + m_tag(M) for s in PAIRS_SLICED]
+        out += [n + m_tag(M) for n in ('pair_no_ws_128_512_128', 'pair_deferred_256_1024_256', 'pair_split16_256_1024_256')]
+        out += ['single_%d_%d_%s' % (s + (r,)) + m_tag(M) for s in SINGLES for r in ('plain', 'res')]
+    for hw in MAPS:
+        out += ['triple_%d_%d_%d_%d_pd%d' % (s + (pd,)) + map_tag(hw) for s in TRIPLES for pd in (1, 2)]
+        out += ['streamed_%d_%d_pd%d' % (s + (pd,)) + map_tag(hw) for s in STREAMED for pd in (1, 2)]
     return out
 
 
@@ -34,7 +56,7 @@ def main(path):
     rnd = lambda *s: torch.randn(*s, generator=g).to(DEV)
     res = {}
 
-    def pair(cm, co, cn, ws=False, parts=0, rparts=0, split16=False, launches=1):
+    def pair(M, cm, co, cn, ws=False, parts=0, rparts=0, split16=False, launches=1):
         """the pair through its descriptor; returns y and t of every launch (the same workspace for all of them)"""
         w3, w1 = rnd(co, cm) / cm ** 0.5, rnd(cn, co) / co ** 0.5
         b3, b1 = rnd(co), rnd(cn)
@@ -62,27 +84,31 @@ def main(path):
             outs.append(ovf)
         return outs
 
-    for s in PAIRS_UNSLICED:
-        res['pair_%d_%d_%d' % s] = pair(*s)
-    for s in PAIRS_SLICED:
-        res['pair_sliced_%d_%d_%d' % s] = pair(*s, ws=True, launches=2)
-    res['pair_no_ws_128_512_128'] = pair(128, 512, 128)
-    res['pair_deferred_256_1024_256'] = pair(256, 1024, 256, ws=True, parts=2, rparts=2, launches=2)
-    res['pair_split16_256_1024_256'] = pair(256, 1024, 256, ws=True, split16=True, launches=2)
-    for cin, cm, co, cn in TRIPLES:
-        for pd in (1, 2):
-            x = rnd(1, 5, 5, cin).relu()
-            args = (x, rnd(cm, 9 * cin) / (9 * cin) ** 0.5, rnd(cm), rnd(co, cm) / cm ** 0.5, rnd(co), rnd(1, 5, 5, co),
-                    rnd(cn, co) / co ** 0.5, rnd(cn))
-            res['triple_%d_%d_%d_%d_pd%d' % (cin, cm, co, cn, pd)] = list(hip.pw_triple_f32(*args, pad=(pd, pd), dil=(pd, pd)))
-    for k, n in SINGLES:
-        for r in ('plain', 'res'):
-            x, w, b = rnd(M, k), rnd(n, k) / k ** 0.5, rnd(n)
-            res['single_%d_%d_%s' % (k, n, r)] = [hip.pw_single_f32(x, w, b, res=rnd(M, n) if r == 'res' else None, act=hip.ACT_RELU)]
-    for cin, n in STREAMED:
-        for pd in (1, 2):
-            x, w, b = rnd(1, 5, 5, cin), rnd(n, 9 * cin) / (9 * cin) ** 0.5, rnd(n)
-            res['streamed_%d_%d_pd%d' % (cin, n, pd)] = [hip.stream_conv3x3_f32(x, w, b, (pd, pd), (pd, pd), act=hip.ACT_RELU)]
+    for M in MS:
+        tag = m_tag(M)
+        for s in PAIRS_UNSLICED:
+            res['pair_%d_%d_%d' % s + tag] = pair(M, *s)
+        for s in PAIRS_SLICED:
+            res['pair_sliced_%d_%d_%d' % s + tag] = pair(M, *s, ws=True, launches=2)
+        res['pair_no_ws_128_512_128' + tag] = pair(M, 128, 512, 128)
+        res['pair_deferred_256_1024_256' + tag] = pair(M, 256, 1024, 256, ws=True, parts=2, rparts=2, launches=2)
+        res['pair_split16_256_1024_256' + tag] = pair(M, 256, 1024, 256, ws=True, split16=True, launches=2)
+        for k, n in SINGLES:
+            for r in ('plain', 'res'):
+                x, w, b = rnd(M, k), rnd(n, k) / k ** 0.5, rnd(n)
+                res['single_%d_%d_%s' % (k, n, r) + tag] = [hip.pw_single_f32(x, w, b, res=rnd(M, n) if r == 'res' else None, act=hip.ACT_RELU)]
+    for hw in MAPS:
+        tag = map_tag(hw)
+        for cin, cm, co, cn in TRIPLES:
+            for pd in (1, 2):
+                x = rnd(1, hw, hw, cin).relu()
+                args = (x, rnd(cm, 9 * cin) / (9 * cin) ** 0.5, rnd(cm), rnd(co, cm) / cm ** 0.5, rnd(co), rnd(1, hw, hw, co),
+                        rnd(cn, co) / co ** 0.5, rnd(cn))
+                res['triple_%d_%d_%d_%d_pd%d' % (cin, cm, co, cn, pd) + tag] = list(hip.pw_triple_f32(*args, pad=(pd, pd), dil=(pd, pd)))
+        for cin, n in STREAMED:
+            for pd in (1, 2):
+                x, w, b = rnd(1, hw, hw, cin), rnd(n, 9 * cin) / (9 * cin) ** 0.5, rnd(n)
+                res['streamed_%d_%d_pd%d' % (cin, n, pd) + tag] = [hip.stream_conv3x3_f32(x, w, b, (pd, pd), (pd, pd), act=hip.ACT_RELU)]
     torch.cuda.synchronize()
     assert list(res) == cases()
     torch.save({k: [t.cpu() for t in v] for k, v in res.items()}, path)

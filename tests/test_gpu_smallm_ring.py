@@ -1,8 +1,8 @@
 """The small-M fp32 kernels (csrc/smallm_f32.hip) pin the issue order of their filter ring and start the filter streams before the
 barriers that do not concern them.  Neither touches a floating-point operation or its order: the default library and the
 -DUSOT_RING_UNPINNED build (the schedule without pins and hoisting) must produce the same BITS on every output, y and t
-(scripts/smallm_bits.py has the cases: M = 17 = a full and a ragged pixel tile, 5 x 5 maps, the sliced pairs twice on one
-workspace).  Each library is loaded in a child process of its own; the variant is built once per session."""
+(scripts/smallm_bits.py has the cases: M = 17 = a full and a ragged pixel tile, M = 16 = an exact tile, M = 31 = a 15-row tail,
+5 x 5 and 4 x 4 maps, the sliced pairs twice on one workspace).  Each library is loaded in a child process of its own; the variant is built once per session."""
 import os
 import subprocess
 import sys
@@ -50,6 +50,6 @@ def test_pinned_ring_is_bit_identical_to_the_unpinned_build(both_builds, case):
 def test_sliced_pairs_repeat_on_the_same_workspace(both_builds):
     """second launch on the workspace of the first (tickets reset by the last arriver): the same bits again"""
     for outs in both_builds:
-        for case in ('pair_sliced_128_512_128', 'pair_sliced_256_1024_256', 'pair_deferred_256_1024_256', 'pair_split16_256_1024_256'):
+        for case in smallm_bits.repeated_cases():
             y0, t0, y1, t1 = outs[case][:4]
             assert torch.equal(y0, y1) and torch.equal(t0, t1), case
