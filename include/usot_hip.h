@@ -60,7 +60,11 @@ const char *usot_strerror(int code);
  *   groups > 1 runs `groups` independent problems of identical geometry in one launch
  *   (pointer strides *_gs in elements): the three head towers, connect.py:178-207.
  *   act applies to channels [0, act_split) and act2 to [act_split, Cout) (act_split >= Cout
- *   means act everywhere): lets conf_gen|value_gen run as one Cout=512 conv.
+ *   means act everywhere): lets conf_gen|value_gen run as one Cout=512 conv.  Any act_split is exact; one that is
+ *   not a multiple of 4 (with act != act2) takes the per-channel scalar epilogue instead of the 16-byte one, as do
+ *   y_cstride / y_coff / res_cstride / res_coff / y_gs / r_gs / b_gs that are not multiples of 4 and y_nchw.
+ *   y_cstride / res_cstride 0 = Cout (dense).  A launch writes y[m][y_coff .. y_coff + Cout) of every pixel and
+ *   nothing else: convolutions may fill channel slices of one map side by side.
  *   ksplit > 1 splits the K loop over `ksplit` workgroups; partials go to `ws` and the LAST slice of a
  *   tile to arrive sums them (in slice order) and applies the epilogue inside the same launch.  `ws` holds
  *   usot_conv_ws_floats(d) floats — the slabs [ksplit][groups][M][Cout] followed by one ticket word per tile —
@@ -87,7 +91,7 @@ typedef struct usot_conv_desc {
                        * boundary is the synchronisation: no in-launch combine (4-6 us on the tail of a 20 us launch), no second launch */
     const float *w_scale;   /* w_frag == 2 (the split-fp16 tiles, usot_conv_tile_wfrag(tile) == 2): `w` holds every filter row as hi + lo
                        * fp16 of (row x a power of two) - per k-tile of 64: 64 hi halves then 64 lo halves, the 256 bytes of the fp32 row
-                       * segment - and w_scale[groups][Cout] = 1 / (that power of two x 8) multiplies the finished sums (8 = the
+                       * segment - and w_scale[g * b_gs + co] = 1 / (that power of two x 8) multiplies the finished sums (8 = the
                        * activation scale the kernel applies before it splits them).  NULL otherwise. */
     int32_t x_split;  /* 1: `x` is a SPLIT map - per pixel and 64-channel block the 64 hi halves then the 64 lo halves (fp16) of 8 x value,
                        * the 256 bytes of the fp32 block - as written by a launch with y_split = 1.  Required by, and only valid with, the
@@ -142,9 +146,13 @@ int usot_conv2d_bf16(void *stream, const usot_conv_desc *d);
  * stores the result as fp32 (outputs feeding the fp32 xcorr / reduce / prediction convs, BASELINE
  * config 5).  Also honoured: act / act2 / act_split (NONE, RELU, EXP, CONF) and groups with x_gs,
  * w_gs, b_gs, y_gs (y_gs in OUTPUT elements; no residual with groups).  Not supported: ksplit,
- * y_nchw, channel-offset outputs.  tile: 0 = heuristic, 1..usot_conv_bf16_tile_count().           */
+ * y_nchw, channel-offset outputs.  tile: 0 = heuristic, 1..usot_conv_bf16_tile_count().
+ * Unsupported fields are REJECTED, not ignored - USOT_EINVAL for y_coff != 0, res_coff != 0, y_cstride or res_cstride other
+ * than 0 or Cout (y and res are dense [M][Cout]), and for 0 < act_split < Cout with act != act2 unless act_split % 8 == 0
+ * (the epilogues choose the activation per 8 channels).  r_gs is not read (no residual with groups).                  */
 int usot_conv2d_lp(void *stream, const usot_conv_desc *d, int dtype, int out_f32);
 int usot_conv_bf16_tile_built(int tile);                       /* 1: the low-precision tile id is compiled into this library (cf. usot_conv_tile_built) */
+int usot_conv_bf16_tile_info(int tile, int *bm, int *bn);      /* pixels x channels of a low-precision tile, ids 1..count (cf. usot_conv_tile_info; 0 x 0: not built) */
 int usot_cvt_f32_to_lp(void *stream, const float *src, void *dst, int64_t n, int dtype);
 int usot_maxpool3x3s2_lp(void *stream, const void *x, void *y, int N, int H, int W, int C, int OH, int OW, int dtype);
 int usot_conv_bf16_tile_count(void);

@@ -306,27 +306,42 @@ def _conv_bank(c, tile, w, b):
     return c.put(wd), None, c.put(b), frag
 
 
-def _conv(c, tile, x, bank, *, Cout, KH=1, KW=1, pad=(0, 0), res=None, act=NONE, ksplit=1, y_nchw=False, ovf=None):
-    """one usot_conv2d_f32 launch through its descriptor (stride 1, dilation 1); the split-K workspace holds the NaN pattern in
-    its slabs and zero ticket words, which must be zero again afterwards"""
+def _conv_setup(c, tile, x, bank, *, Cout, KH=1, KW=1, pad=(0, 0), res=None, act=NONE, ksplit=1, y_nchw=False, ovf=None, y=None,
+                xshape=None, **fields):
+    """descriptor of one usot_conv2d_f32 launch (stride 1, dilation 1) -> (desc, y, ws, first ticket word); the split-K workspace
+    holds the NaN pattern in its slabs and zero ticket words.  `y`: an output the caller made (a channel slice, group gaps: the
+    caller checks it, prefill included); `xshape`: (N, H, W, Cin) of one group when x is a flat buffer of several; `fields`: the
+    remaining descriptor fields, passed through (act2, act_split, y_cstride, y_coff, res_cstride, res_coff, groups, *_gs)."""
     wd, sc, bd, frag = bank
-    N, H, W_, Cin = x.shape
+    N, H, W_, Cin = xshape or x.shape
     OH, OW = H + 2 * pad[0] - (KH - 1), W_ + 2 * pad[1] - (KW - 1)
     M = N * OH * OW
-    y = c.out((N, Cout, OH, OW) if y_nchw else (N, OH, OW, Cout))
-    ws = None
+    G = fields.get('groups', 1)
+    if y is None:
+        assert G == 1
+        y = c.out((N, Cout, OH, OW) if y_nchw else (N, OH, OW, Cout))
+    ws, tick = None, 0
     if ksplit > 1:
-        ws = c.out((ksplit * M * Cout + ((M + 15) // 16) * ((Cout + 31) // 32),))
-        ws[ksplit * M * Cout:].zero_()
+        tick = ksplit * G * M * Cout
+        ws = c.out((tick + G * ((M + 15) // 16) * ((Cout + 31) // 32),))
+        ws[tick:].zero_()
     d = hip.conv_desc(x.data_ptr(), wd.data_ptr(), bd.data_ptr(), y.data_ptr(), N=N, H=H, W=W_, Cin=Cin, OH=OH, OW=OW, Cout=Cout, KH=KH, KW=KW,
                       pad=pad, res=res.data_ptr() if res is not None else None, act=act, tile=tile, ksplit=ksplit,
                       ws=ws.data_ptr() if ws is not None else None, y_nchw=int(y_nchw), w_frag=frag,
-                      w_scale=sc.data_ptr() if sc is not None else None, ovf=ovf.data_ptr() if ovf is not None else None)
-    hip.check(hip.lib().usot_conv2d_f32(hip.stream(), C.byref(d)), 'usot_conv2d_f32 tile %d M = %d Cout = %d ksplit = %d' % (tile, M, Cout, ksplit))
-    no_nan(y)
+                      w_scale=sc.data_ptr() if sc is not None else None, ovf=ovf.data_ptr() if ovf is not None else None, **fields)
+    return d, y, ws, tick
+
+
+def _conv(c, tile, x, bank, *, Cout, ksplit=1, y=None, **kw):
+    """one usot_conv2d_f32 launch through its descriptor (_conv_setup); no NaN in an output made here, and the ticket words of
+    the split-K workspace must be zero again afterwards"""
+    d, out, ws, tick = _conv_setup(c, tile, x, bank, Cout=Cout, ksplit=ksplit, y=y, **kw)
+    hip.check(hip.lib().usot_conv2d_f32(hip.stream(), C.byref(d)), 'usot_conv2d_f32 tile %d Cout = %d ksplit = %d' % (tile, Cout, ksplit))
+    if y is None:
+        no_nan(out)
     if ws is not None:
-        assert not bool(ws[ksplit * M * Cout:].view(torch.int32).any()), (tile, M, Cout, ksplit)
-    return y
+        assert not bool(ws[tick:].view(torch.int32).any()), (tile, Cout, ksplit)
+    return out
 
 
 def _pw_problem(M, Cout, seed):

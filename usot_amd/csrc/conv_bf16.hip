@@ -1045,6 +1045,13 @@ __global__ __launch_bounds__(256, USOT_STEM_MINW) void stem_pool_lp_kernel(
 
 extern "C" int usot_conv_bf16_tile_count(void) { return kNumTilesB; }
 extern "C" int usot_conv_bf16_tile_built(int tile) { return (tile >= 1 && tile <= kNumTilesB && kTilesB[tile - 1].fn) ? 1 : 0; }
+extern "C" int usot_conv_bf16_tile_info(int tile, int *bm, int *bn)
+{
+    if (tile < 1 || tile > kNumTilesB) return USOT_EINVAL;
+    if (bm) *bm = kTilesB[tile - 1].bm;
+    if (bn) *bn = kTilesB[tile - 1].bn;
+    return USOT_OK;
+}
 
 /* bf16|fp16 NHWC conv: x/w/res/y in the storage type (uint16), bias fp32.  Uses the fields N..dil_w,
  * act/act2/act_split, groups (+ x_gs, w_gs, b_gs, y_gs), tile of usot_conv_desc; y dense NHWC
@@ -1059,6 +1066,13 @@ extern "C" int usot_conv2d_lp(void *stream, const usot_conv_desc *d, int dtype, 
     if (d->Cin <= 0 || (d->Cin % BKB) || d->Cout <= 0 || (d->Cout & 3) || d->N <= 0) return USOT_EINVAL;
     if (d->ksplit > 1 || d->y_nchw || d->groups < 0 || (d->groups > 1 && d->res)) return USOT_EINVAL;
     if (d->act < USOT_ACT_NONE || d->act > USOT_ACT_CONF) return USOT_EINVAL;
+    // the kernels store a dense map at y + m * Cout + co and read the residual the same way: a channel slice on either side is an
+    // fp32-path feature, and asking for one here must not come back as a dense map in the wrong place
+    if (d->y_coff != 0 || (d->y_cstride != 0 && d->y_cstride != d->Cout)) return USOT_EINVAL;
+    if (d->res_coff != 0 || (d->res_cstride != 0 && d->res_cstride != d->Cout)) return USOT_EINVAL;
+    // the epilogues pick the activation once per 8 (LDS epilogue) or 4 (piece epilogue) channels: a split inside such a group
+    // would give its upper channels the wrong activation
+    if (d->act_split > 0 && d->act_split < d->Cout && d->act != d->act2 && (d->act_split & 7)) return USOT_EINVAL;
     const int oh = (d->H + 2 * d->pad_h - d->dil_h * (d->KH - 1) - 1) / d->stride + 1;
     const int ow = (d->W + 2 * d->pad_w - d->dil_w * (d->KW - 1) - 1) / d->stride + 1;
     if (oh != d->OH || ow != d->OW || oh <= 0 || ow <= 0) return USOT_EINVAL;

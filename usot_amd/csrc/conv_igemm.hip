@@ -2728,7 +2728,10 @@ int fill_params(const usot_conv_desc *d, ConvK &p)
                   (!d->res || (p.res_cstride % 4 == 0 && p.res_coff % 4 == 0)) &&
                   ((uintptr_t)d->y % 16 == 0) && (!d->res || (uintptr_t)d->res % 16 == 0) &&
                   (!d->bias || (uintptr_t)d->bias % 16 == 0) &&
-                  (d->y_gs % 4 == 0) && (d->r_gs % 4 == 0) && (d->b_gs % 4 == 0);
+                  (d->y_gs % 4 == 0) && (d->r_gs % 4 == 0) && (d->b_gs % 4 == 0) &&
+                  // the vector epilogues pick the activation once per group of four channels, from the group's first one: a split
+                  // inside a group takes the per-channel scalar epilogue (the frame's act_split = 256 keeps the vector path)
+                  (d->act_split <= 0 || d->act_split % 4 == 0 || d->act == d->act2);
     if (((uintptr_t)d->x % 16) || ((uintptr_t)d->w % 16) || (d->x_gs % 4) || (d->w_gs % 4))
         return USOT_EINVAL;
     return USOT_OK;

@@ -15,7 +15,7 @@ ACT_NONE, ACT_RELU, ACT_EXP, ACT_CONF = 0, 1, 2, 3
 
 EXPORTS = (
     'usot_abi_version', 'usot_device_guard', 'usot_device_slot', 'usot_strerror', 'usot_conv2d_f32', 'usot_conv_tile_count',
-    'usot_conv_tile_info', 'usot_conv_tile_built', 'usot_experiments_built', 'usot_conv_bf16_tile_built', 'usot_conv_tile_name', 'usot_conv_tile_wfrag', 'usot_conv_tile_xsplit', 'usot_conv_tile_kreq', 'usot_conv_tile_streamk', 'usot_conv_streamk_ws_floats', 'usot_conv_pack_wfrag_f32', 'usot_conv_ws_floats', 'usot_stem_conv_f32', 'usot_maxpool3x3s2_f32',
+    'usot_conv_tile_info', 'usot_conv_tile_built', 'usot_experiments_built', 'usot_conv_bf16_tile_built', 'usot_conv_bf16_tile_info', 'usot_conv_tile_name', 'usot_conv_tile_wfrag', 'usot_conv_tile_xsplit', 'usot_conv_tile_kreq', 'usot_conv_tile_streamk', 'usot_conv_streamk_ws_floats', 'usot_conv_pack_wfrag_f32', 'usot_conv_ws_floats', 'usot_stem_conv_f32', 'usot_maxpool3x3s2_f32',
     'usot_xcorr_depthwise_f32', 'usot_groupdw_f32', 'usot_conf_fusion_reduce_f32',
     'usot_prroi_pool_forward_f32', 'usot_prroi_pool_backward_f32', 'usot_prroi_pool_coor_backward_f32', 'usot_permute4_f32', 'usot_decode_f32',
     'usot_plan_create', 'usot_plan_destroy', 'usot_plan_add_conv', 'usot_plan_add_stem',
@@ -237,6 +237,7 @@ def lib():
         L.usot_decode_dev_f32.argtypes = ([C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_float] + [C.c_double] * 2
                                           + [C.c_void_p] * 2)
         L.usot_conv_tile_info.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.usot_conv_bf16_tile_info.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.usot_conv_pack_wfrag_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 2
         L.usot_conv_tile_kreq.argtypes = [C.c_int, C.POINTER(C.c_int)]
         L.usot_conv_streamk_ws_floats.argtypes = [C.c_void_p, C.c_int, C.c_int]
@@ -366,6 +367,19 @@ def tile_table():
             continue
         bm, bn = C.c_int(), C.c_int()
         L.usot_conv_tile_info(i, C.byref(bm), C.byref(bn))
+        out[i] = (bm.value, bn.value)
+    return out
+
+
+def tile_table_lp():
+    """{low-precision tile id: (bm, bn)} of the tiles of usot_conv2d_lp this library holds (usot_conv_bf16_tile_info)."""
+    L = lib()
+    out = {}
+    for i in range(1, L.usot_conv_bf16_tile_count() + 1):
+        if not L.usot_conv_bf16_tile_built(i):
+            continue
+        bm, bn = C.c_int(), C.c_int()
+        check(L.usot_conv_bf16_tile_info(i, C.byref(bm), C.byref(bn)), 'usot_conv_bf16_tile_info')
         out[i] = (bm.value, bn.value)
     return out
 
