@@ -102,6 +102,17 @@ typedef struct usot_conv_desc {
                        * sums is not finite - what an activation beyond the fp16 window (|x| >= 8 188: hi = inf, lo = -inf) or a non-finite
                        * input turns every sum it enters into - BEFORE bias / activation / split-K slabs see the sum (a ReLU would turn the
                        * NaN into a finite 0).  The caller re-runs the work on the exact-fp32 tiles (usot_amd/engine.py: Session, Engine.track) */
+    const int32_t *n_dyn;   /* NULL (off), or a DEVICE word read by the launch: a run-time image count.  Images
+                       * [0, clamp(*n_dyn - n_first, 0, N)) of this problem are computed; the rows of the others are neither read nor
+                       * written (a tile that straddles the limit treats them as it treats rows past N * OH * OW; they never reach `ovf`),
+                       * and a workgroup whose tile lies wholly past the limit leaves before it touches LDS, `ws` or a ticket.  `ws`, its
+                       * slab strides and the ticket indices are those of the static N: every k-slice of a tile takes the same decision and
+                       * the tickets stay zero.  Lets ONE captured launch serve a number of images decided on the device (the session's
+                       * distinct memory rows, usot_rows_append_gather_dedupe_f32).  Producer / consumer tiles only (conv_igemm_f32_v3,
+                       * exact-fp32 and split-fp16 - the ids with usot_conv_tile_dyn(tile) == 1), not with `defer`: USOT_EINVAL otherwise.
+                       * In a batched launch the problems with the higher n_first should come last: their workgroups then own the
+                       * highest block ids and the empty ones drain behind the working ones */
+    int32_t n_first;  /* with n_dyn: the index, in the caller's image numbering, of this problem's first image (>= 0) */
 } usot_conv_desc;
 
 int usot_conv2d_f32(void *stream, const usot_conv_desc *d);
@@ -122,6 +133,7 @@ int usot_conv_tile_info(int tile, int *bm, int *bn);           /* tile ids are 1
 int usot_conv_tile_built(int tile);                            /* 1: compiled into this library (the routed tiles; every id with -DUSOT_EXPERIMENTS) */
 int usot_experiments_built(void);                              /* 1: the library was built with -DUSOT_EXPERIMENTS */
 int usot_conv_tile_name(int tile, char *buf, int len);         /* kernel symbol of the tile */
+int usot_conv_tile_dyn(int tile);                              /* 1: the tile honours usot_conv_desc.n_dyn (run-time image count) */
 int usot_conv_tile_xsplit(int tile);                           /* 1: the tile reads a split input map (usot_conv_desc.x_split) */
 int usot_conv_tile_wfrag(int tile);                            /* 1: the tile streams its filters in fragment order; 2: split-fp16 bank + w_scale */
 /* weight-stationary tiles (filters held in registers, k split over the 8 waves of a workgroup) serve ONE K each: returns it
@@ -419,6 +431,12 @@ int usot_groupdw_multi_f32(void *stream, const usot_groupdw_desc *d, int nseg);
  * arithmetic, one rounding at the store (the batched mixed-precision heads of BASELINE configs[4] feed these maps to fp16
  * convolutions).  25- and 27-wide responses only. */
 int usot_groupdw_multi_lp(void *stream, const usot_groupdw_desc *d, int nseg, int out_dtype);
+/* usot_groupdw_multi_f32 with the number of live samples of its LAST segment read from DEVICE memory at run time: *last_count,
+ * clamped to [0, d[nseg - 1].S].  The grid stays sized for d[nseg - 1].S; workgroups of the samples past the count leave at once,
+ * their outputs keep their old contents.  The 5 x 1 strips kernel (what a single frame runs) only: USOT_EINVAL where another
+ * variant would run.  last_count == NULL: the static launch. */
+int usot_groupdw_multi_dyn_f32(void *stream, const usot_groupdw_desc *d, int nseg, const int32_t *last_count);
+int usot_plan_add_groupdw_multi_dyn(void *plan, const usot_groupdw_desc *d, int nseg, const int32_t *last_count);
 
 /* ---- Conf_Fusion reduction (connect.py:132-142): cv NHWC [B*M][P][2C] holding
  * conf = exp(clamp) in channels [0,C) and value in [C,2C) -> out [B][P][C] =
@@ -426,6 +444,11 @@ int usot_groupdw_multi_lp(void *stream, const usot_groupdw_desc *d, int nseg, in
 int usot_conf_fusion_reduce_f32(void *stream, const float *cv, float *out,
                                 int B, int M, int P, int C);
 int usot_conf_fusion_reduce_lp(void *stream, const void *cv, int in_dtype, void *out, int B, int M, int P, int C, int out_dtype);   /* cv fp32 (0) | fp16 (1) | bf16 (2); out fp16 (1) | bf16 (2) */
+/* the fp32 reduction through a slot map in DEVICE memory: slot m reads map map[m] (int32[M], entries in [0, M)) of its batch
+ * element's block of M maps.  The sums run over the M slots in slot order, exactly as the static kernel sums a tensor gathered by
+ * `map` - no weighting by multiplicity.  map == NULL: usot_conf_fusion_reduce_f32. */
+int usot_conf_fusion_reduce_map_f32(void *stream, const float *cv, float *out, int B, int M, int P, int C, const int32_t *map);
+int usot_plan_add_conf_reduce_map(void *plan, const float *cv, float *out, int B, int M, int P, int C, const int32_t *map);
 
 /* ---- Precise RoI Pooling forward.  Replaces PrRoIPoolingForwardGpu
  * (prroi_pooling_gpu_impl.cuh:20-28 / .cu:149-212,387-402) with explicit strides so the
@@ -603,6 +626,16 @@ int usot_rows_append_gather_f32(void *stream, const float *const *fresh, float *
                                 const int32_t *row_len, const int32_t *idx_dev, int n_pick, int slot_pos);
 int usot_plan_add_rows_append_gather(void *plan, const float *const *fresh, float *const *bank, float *const *picked,
                                      const int32_t *row_len, const int32_t *idx_dev, int n_pick, int slot_pos);
+/* the same launch on DISTINCT picked rows only.  With first(j) = the smallest i <= j whose row equals row j and u(j) = the rank of
+ * first(j) among first occurrences (distinct rows keep their order of first appearance, D of them), only rows j == first(j) are
+ * copied, to picked[g][u(j)]; rows >= D of the picked buffers are NOT written.  mem_map (DEVICE memory, int32[1 + n_pick]) receives
+ * mem_map[0] = D and mem_map[1 + j] = u(j): the sample count, image count and slot map of the launches behind it
+ * (usot_groupdw_multi_dyn_f32, usot_conv_desc.n_dyn, usot_conf_fusion_reduce_map_f32).  The append half and the "a picked row that
+ * is the appended row comes from `fresh`" rule are unchanged. */
+int usot_rows_append_gather_dedupe_f32(void *stream, const float *const *fresh, float *const *bank, float *const *picked,
+                                       const int32_t *row_len, const int32_t *idx_dev, int n_pick, int slot_pos, int32_t *mem_map);
+int usot_plan_add_rows_append_gather_dedupe(void *plan, const float *const *fresh, float *const *bank, float *const *picked,
+                                            const int32_t *row_len, const int32_t *idx_dev, int n_pick, int slot_pos, int32_t *mem_map);
 /* ---- lock-step multi-video tracking (csrc/multitrack.hip): B videos ("slots") of one instance size step together in one
  * frame graph.  Each kernel is ONE launch per step whatever B.  The step's control block `ctl` (pinned, device-mapped host
  * memory, or device memory) is a USOT_STEP_HDR_BYTES header - the step tag, a double, at offset 0 - followed by B

@@ -54,6 +54,8 @@ struct ConvK {
     const float *zero;                  // PF = 6: 16 zero bytes, the source of padding taps for the activation DMA
     int x_split, y_split;               // the input map arrives / the result leaves in the split-fp16 layout (usot_conv_desc)
     int *ovf;                           // split-fp16 tiles: sticky "a finished sum was not finite" word (usot_conv_desc.ovf) or nullptr
+    const int *n_dyn;                   // v3 tiles: nullptr, or a device word with a run-time image count (usot_conv_desc.n_dyn): images
+    int n_first;                        // [0, clamp(*n_dyn - n_first, 0, N)) of this problem are live, the rest is neither read nor written
 };
 
 // Up to four convolutions of DIFFERENT geometry in one launch (same tile shape): the shortcut
@@ -106,8 +108,9 @@ __device__ __forceinline__ void ws_store1(const ConvK &p, long elem, float v)
 // behind the slabs, are zero before the first launch (the engine zero-fills the workspace) and are reset by
 // the last arriver, so every launch — and every graph replay — finds them zero.
 template <int BM, int BN>
-__device__ __forceinline__ void splitk_combine(const ConvK &p, int g, int t0, int tiles, int bm0, int bn0, int tid, int *flag)
+__device__ __forceinline__ void splitk_combine(const ConvK &p, int g, int t0, int tiles, int bm0, int bn0, int tid, int *flag, int mlim = -1)
 {
+    const int ML = mlim < 0 ? p.M : mlim;     // rows the launch computes (n_dyn: fewer than M; slab strides and tickets keep the static M)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) {
@@ -129,7 +132,7 @@ __device__ __forceinline__ void splitk_combine(const ConvK &p, int g, int t0, in
         for (int idx = tid; idx < BM * (BN / 4); idx += 256) {
             const int row = idx / (BN / 4), c4 = (idx - row * (BN / 4)) * 4;
             const int m = bm0 + row, co = bn0 + c4;
-            if (m >= p.M || co >= p.Cout) continue;
+            if (m >= ML || co >= p.Cout) continue;
             const long el = (long)g * p.M * p.Cout + (long)m * p.Cout + co;
             f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
             for (int ks = 0; ks < p.ksplit; ++ks)
@@ -148,7 +151,7 @@ __device__ __forceinline__ void splitk_combine(const ConvK &p, int g, int t0, in
     for (int idx = tid; idx < BM * BN; idx += 256) {
         const int row = idx / BN, cc = idx - row * BN;
         const int m = bm0 + row, c = bn0 + cc;
-        if (m >= p.M || c >= p.Cout) continue;
+        if (m >= ML || c >= p.Cout) continue;
         float sum = 0.f;
         for (int ks = 0; ks < p.ksplit; ++ks) sum += __hip_atomic_load(ws0 + ks * slab + (long)m * p.Cout + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (bg) sum += bg[c];
@@ -748,6 +751,8 @@ __global__ __launch_bounds__(PF == 6 ? 64 * WM * WN + 768 : 64 * WM * WN + 64 * 
     for (int q = 1; q < 4; ++q)
         if (q < bt.n && (int)blockIdx.x >= bt.start[q]) pi = q;
     const ConvK &p = bt.p[pi];
+    // run-time image count (usot_conv_desc.n_dyn): the load is issued first and used behind the index prologue
+    const int dyn_n = p.n_dyn ? *p.n_dyn : 0;
     const int bid0 = (int)blockIdx.x - bt.start[pi];
     // WM x WN consumer wavefronts: 4 (one per SIMD) or 8 (two per SIMD, round 5: the same tile in smaller wave tiles, nothing to
     // exchange).  Probe (scripts/probes/coissue_probe.hip, inline-asm reads, independent accumulators): a SIBLING wave's VALU / SALU /
@@ -818,6 +823,11 @@ __global__ __launch_bounds__(PF == 6 ? 64 * WM * WN + 768 : 64 * WM * WN + 64 * 
     const int kt0 = (int)((long)KT * ks / p.ksplit);
     const int kt1 = (int)((long)KT * (ks + 1) / p.ksplit);
     const int nt = kt1 - kt0;
+    // ML = the rows this launch computes: M, or with n_dyn the rows of the live images.  A workgroup whose tile lies past them leaves
+    // here - before LDS, the split-K slabs, the tickets or the ovf word are touched (every k-slice of a tile takes the same decision, so
+    // the tickets stay zero); a tile that straddles ML treats the rows past it as rows past M: not loaded (zeros), not stored
+    const int ML = p.n_dyn ? min(max(dyn_n - p.n_first, 0), p.N) * p.P : p.M;
+    if (bm0 >= ML) return;
 
     if constexpr (WDMA) {
         if ((int)threadIdx.x >= CT + NPTL) {
@@ -854,7 +864,7 @@ __global__ __launch_bounds__(PF == 6 ? 64 * WM * WN + 768 : 64 * WM * WN + 64 * 
                     const int piece = dwv + q * NDW, c = 64 * piece + lane;
                     xlive[q] = piece < NPX && c < NCHX;
                     const int row = c / 17, ch = c - row * 17, m = bm0 + row;
-                    xrow[q] = xlive[q] && ch < 16 && m < p.M;          // a real pixel and a data chunk (else: zeros)
+                    xrow[q] = xlive[q] && ch < 16 && m < ML;          // a real pixel and a data chunk (else: zeros)
                     const int mm = xrow[q] ? m : 0;
                     const int n = mm / p.P, pix = mm - n * p.P;
                     const int oh = pix / p.OW, ow = pix - oh * p.OW;
@@ -949,7 +959,7 @@ __global__ __launch_bounds__(PF == 6 ? 64 * WM * WN + 768 : 64 * WM * WN + 64 * 
         for (int i = 0; i < XI; ++i) {
             const int row = lr + RPP * i;
             const int m = bm0 + row;
-            x_ok[i] = (row < BM) && (m < p.M);
+            x_ok[i] = (row < BM) && (m < ML);
             const int mm = x_ok[i] ? m : 0;
             const int n = mm / p.P, pix = mm - n * p.P;
             const int oh = pix / p.OW, ow = pix - oh * p.OW;
@@ -1221,7 +1231,7 @@ __global__ __launch_bounds__(PF == 6 ? 64 * WM * WN + 768 : 64 * WM * WN + 64 * 
 #pragma unroll
         for (int j = 0; j < TM; ++j) {
             const int m = bm0 + (wm * TM + j) * 16 + l15;
-            pr[i][j] = (cok && p.res && m < p.M)
+            pr[i][j] = (cok && p.res && m < ML)
                            ? *(const f32x4 *)(p.res + (long)g * p.r_gs + (long)m * p.res_cstride + p.res_coff + co)
                            : f32x4{0.f, 0.f, 0.f, 0.f};
         }
@@ -1374,7 +1384,7 @@ __global__ __launch_bounds__(PF == 6 ? 64 * WM * WN + 768 : 64 * WM * WN + 64 * 
 #pragma unroll
         for (int j = 0; j < TM; ++j) {
             const int m = bm0 + (wm * TM + j) * 16 + l15;
-            if (m >= p.M) continue;
+            if (m >= ML) continue;
 #pragma unroll
             for (int i = 0; i < TN; ++i) {
                 const int co = bn0 + (wn * TN + i) * 16 + quad * 4;
@@ -1387,7 +1397,7 @@ __global__ __launch_bounds__(PF == 6 ? 64 * WM * WN + 768 : 64 * WM * WN + 64 * 
                 }
             }
         }
-        if (p.combine) splitk_combine<BM, BN>(p, g, t0, tiles, bm0, bn0, tid, (int *)smem);
+        if (p.combine) splitk_combine<BM, BN>(p, g, t0, tiles, bm0, bn0, tid, (int *)smem, ML);
         return;
     }
     const float *__restrict__ bg = p.bias ? p.bias + (long)g * p.b_gs : nullptr;
@@ -1396,7 +1406,7 @@ __global__ __launch_bounds__(PF == 6 ? 64 * WM * WN + 768 : 64 * WM * WN + 64 * 
 #pragma unroll
     for (int j = 0; j < TM; ++j) {
         const int m = bm0 + (wm * TM + j) * 16 + l15;
-        if (m >= p.M) continue;
+        if (m >= ML) continue;
 #pragma unroll
         for (int i = 0; i < TN; ++i) {
             const int co = bn0 + (wn * TN + i) * 16 + quad * 4;
@@ -2629,6 +2639,14 @@ extern "C" int usot_conv_tile_wfrag(int tile)
     return kTiles[tile - 1].wfrag;
 }
 
+/* 1 when the tile honours usot_conv_desc.n_dyn: the producer / consumer family (conv_igemm_f32_v3), exact-fp32 and split-fp16 */
+extern "C" int usot_conv_tile_dyn(int tile)
+{
+    if (tile < 1 || tile > kNumTiles) return 0;
+    const TileCfg &tc = kTiles[tile - 1];
+    return (tc.fn && !tc.nst && tc.stages == 3 && tc.ksw == 1 && tc.threads >= 512 && tc.wfrag != 1) ? 1 : 0;
+}
+
 extern "C" int usot_conv_tile_xsplit(int tile) { return (tile >= 1 && tile <= kNumTiles && kTiles[tile - 1].wfrag == 2 && kTiles[tile - 1].dw == 6) ? 1 : 0; }
 
 /* weight-stationary tiles serve ONE reduction length: K the tile requires (0: any K the other rules allow); their other
@@ -2724,6 +2742,8 @@ int fill_params(const usot_conv_desc *d, ConvK &p)
     p.cchunks = d->Cin / 32;
     p.KT = d->KH * d->KW * p.cchunks;
     p.wscale = nullptr; p.zero = nullptr; p.x_split = p.y_split = 0; p.ovf = nullptr;
+    if (d->n_dyn && (((uintptr_t)d->n_dyn & 3) || d->n_first < 0)) return USOT_EINVAL;
+    p.n_dyn = (const int *)d->n_dyn; p.n_first = d->n_first;
     p.vec_store = !d->y_nchw && (p.y_cstride % 4 == 0) && (p.y_coff % 4 == 0) &&
                   (!d->res || (p.res_cstride % 4 == 0 && p.res_coff % 4 == 0)) &&
                   ((uintptr_t)d->y % 16 == 0) && (!d->res || (uintptr_t)d->res % 16 == 0) &&
@@ -2829,6 +2849,10 @@ extern "C" int usot_conv2d_batch_f32(void *stream, const usot_conv_desc *d, int 
     const TileCfg &tc = kTiles[tile - 1];
     if (!tc.fn && !tc.skfn) return USOT_ENOTBUILT;
     long blocks = 0;
+    // run-time image counts (usot_conv_desc.n_dyn): the producer / consumer tiles (conv_igemm_f32_v3, exact and split-fp16) only
+    const bool v3tile = usot_conv_tile_dyn(tile) == 1;
+    for (int i = 0; i < n; ++i)
+        if (d[i].n_dyn && (!v3tile || d[i].defer)) return USOT_EINVAL;
     if (tc.skfn) {                         // persistent stream-K: a resident set of workgroups shares the (tile, k-tile) units
         SkInfo sk;
         const int64_t need = sk_plan(tc, d, n, bt, sk);

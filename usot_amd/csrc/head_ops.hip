@@ -34,9 +34,12 @@ template <int IT> __device__ __forceinline__ f32x4 cf_load4(const void *base, lo
     }
 }
 
-template <int OT, int IT = 0>
+// MAP (usot_conf_fusion_reduce_map_f32): slot m reads map `map[m]` of its batch element's M-map block.  The sums still run over the M
+// SLOTS in slot order - the reference's summation order, no weighting by multiplicity; a map that serves several slots is read again
+// (L2 hits).  MAP = false: `map` is not read.
+template <int OT, int IT = 0, bool MAP = false>
 __global__ __launch_bounds__(256) void conf_fusion_reduce_kernel(
-    const void *__restrict__ cv, float *__restrict__ out, int B, int M, int P, int C4)
+    const void *__restrict__ cv, float *__restrict__ out, int B, int M, int P, int C4, const int *__restrict__ map)
 {
     const long total = (long)B * P * C4;
     for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
@@ -47,11 +50,12 @@ __global__ __launch_bounds__(256) void conf_fusion_reduce_kernel(
         f32x4 den = {0.f, 0.f, 0.f, 0.f}, num = {0.f, 0.f, 0.f, 0.f};
         const long base = ((long)b * M * P + pix) * 2 * C4 * 4 + c * 4;        // element index of this lane's four conf values
         const long mstride = (long)P * 2 * C4 * 4;
-        for (int m = 0; m < M; ++m) den += cf_load4<IT>(cv, base + m * mstride);
+        auto at = [&](int m) { return base + (MAP ? map[m] : m) * mstride; };
+        for (int m = 0; m < M; ++m) den += cf_load4<IT>(cv, at(m));
         // same association as the reference: normalise each conf, then weight and add
         for (int m = 0; m < M; ++m) {
-            const f32x4 c4 = cf_load4<IT>(cv, base + m * mstride);        // L1/L2 hit
-            const f32x4 v4 = cf_load4<IT>(cv, base + m * mstride + C4 * 4);
+            const f32x4 c4 = cf_load4<IT>(cv, at(m));        // L1/L2 hit
+            const f32x4 v4 = cf_load4<IT>(cv, at(m) + C4 * 4);
             num += (c4 / den) * v4;
         }
         if constexpr (OT == 0) {
@@ -554,6 +558,62 @@ __global__ __launch_bounds__(256) void rows_append_gather_kernel(const RowsAG k,
     }
 }
 
+// The same launch on DISTINCT rows only (usot_rows_append_gather_dedupe_f32): the frame's picks repeat rows (the reference's index
+// formula yields [0, 1, 2 + best, 2 + last x 4] in steady state), and everything downstream of the gather is a pure function of the
+// row.  Every workgroup derives, from the picks it already holds in LDS, first(j) = the smallest i <= j with rows[i] == rows[j] and
+// u(j) = the rank of first(j) among first occurrences (distinct rows keep their order of first appearance); only leaders
+// (first(j) == j) are copied, to picked[g][u(j)], rows >= D of the picked buffers are not written.  Workgroup (0, 0) publishes
+// mem_map[0] = D, mem_map[1 + j] = u(j) for the launches behind it (GroupDW's sample count, the conv's image count, the reduction's
+// slot map).  The grid is sized for n_pick rows: workgroups past D rows find an empty loop.
+__global__ __launch_bounds__(256) void rows_append_gather_dedupe_kernel(const RowsAG k, const int *__restrict__ idx, int *__restrict__ mem_map)
+{
+    __shared__ int rows[33], first[32], lead[32], nd;
+    if (threadIdx.x < k.n_pick) rows[threadIdx.x] = idx[threadIdx.x];
+    if (threadIdx.x == 32) rows[32] = idx[k.slot_pos];
+    __syncthreads();
+    if (threadIdx.x < k.n_pick) {
+        int f = threadIdx.x;
+        for (int i = (int)threadIdx.x - 1; i >= 0; --i)
+            if (rows[i] == rows[threadIdx.x]) f = i;
+        first[threadIdx.x] = f;
+    }
+    __syncthreads();
+    if (threadIdx.x < k.n_pick) {
+        const int f = first[threadIdx.x];
+        int u = 0;
+        for (int i = 0; i < f; ++i) u += first[i] == i ? 1 : 0;
+        if (f == (int)threadIdx.x) lead[u] = f;
+        if (threadIdx.x == (unsigned)k.n_pick - 1) {
+            int d = u + 1;                             // leaders behind first(n_pick - 1)
+            for (int i = f + 1; i < k.n_pick; ++i) d += first[i] == i ? 1 : 0;
+            nd = d;
+            if (blockIdx.x == 0 && blockIdx.y == 0) mem_map[0] = d;
+        }
+        if (blockIdx.x == 0 && blockIdx.y == 0) mem_map[1 + threadIdx.x] = u;
+    }
+    __syncthreads();
+    const int slot = rows[32];
+    const int job = blockIdx.y;
+    if (job < 4) {
+        const int rl = k.row_len4[job];
+        const f32x4 *__restrict__ src = (const f32x4 *)k.fresh[job];
+        f32x4 *__restrict__ dst = (f32x4 *)k.bank[job] + (long)slot * rl;
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < rl; i += gridDim.x * 256) dst[i] = src[i];
+        return;
+    }
+    const int b = job - 3;
+    const int rl = k.row_len4[b];
+    const f32x4 *__restrict__ fresh = (const f32x4 *)k.fresh[b];
+    const f32x4 *__restrict__ bank = (const f32x4 *)k.bank[b];
+    f32x4 *__restrict__ dst = (f32x4 *)k.picked[b - 1];
+    const int total = nd * rl;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+        const int r = i / rl, e = i - r * rl;
+        const int row = rows[lead[r]];
+        dst[i] = row == slot ? fresh[e] : bank[(long)row * rl + e];
+    }
+}
+
 // ---- SiamFC crop on the device (lib/utils/track_utils.py:30-119): window extraction with
 // mean-colour padding, OpenCV-style fixed-point bilinear resize (the arithmetic restated in
 // usot_amd/hostutils.py::resize_bilinear_u8) and HWC uint8 -> CHW float32, one thread per
@@ -701,7 +761,21 @@ extern "C" int usot_conf_fusion_reduce_f32(void *stream, const float *cv, float 
     const long total = (long)B * P * (C / 4);
     const int blocks = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
     hipLaunchKernelGGL((conf_fusion_reduce_kernel<0, 0>), dim3(blocks), dim3(256), 0, (hipStream_t)stream,
-                       (const void *)cv, out, B, M, P, C / 4);
+                       (const void *)cv, out, B, M, P, C / 4, (const int *)nullptr);
+    USOT_CHECK_LAUNCH();
+    return USOT_OK;
+}
+
+/* the fp32 reduction through a slot map in DEVICE memory (int32[M], every entry in [0, M)): slot m reads map map[m] */
+extern "C" int usot_conf_fusion_reduce_map_f32(void *stream, const float *cv, float *out, int B, int M, int P, int C, const int32_t *map)
+{
+    if (!map) return usot_conf_fusion_reduce_f32(stream, cv, out, B, M, P, C);
+    if (!cv || !out || B <= 0 || M <= 0 || P <= 0 || C <= 0 || (C & 3)) return USOT_EINVAL;
+    if (((uintptr_t)cv % 16) || ((uintptr_t)out % 16) || ((uintptr_t)map % 4)) return USOT_EINVAL;
+    const long total = (long)B * P * (C / 4);
+    const int blocks = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
+    hipLaunchKernelGGL((conf_fusion_reduce_kernel<0, 0, true>), dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                       (const void *)cv, out, B, M, P, C / 4, (const int *)map);
     USOT_CHECK_LAUNCH();
     return USOT_OK;
 }
@@ -715,7 +789,7 @@ extern "C" int usot_conf_fusion_reduce_lp(void *stream, const void *cv, int in_d
     const long total = (long)B * P * (C / 4);
     const int blocks = (int)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
     hipStream_t s = (hipStream_t)stream;
-#define CF_LAUNCH(OT, IT) hipLaunchKernelGGL((conf_fusion_reduce_kernel<OT, IT>), dim3(blocks), dim3(256), 0, s, cv, (float *)out, B, M, P, C / 4)
+#define CF_LAUNCH(OT, IT) hipLaunchKernelGGL((conf_fusion_reduce_kernel<OT, IT>), dim3(blocks), dim3(256), 0, s, cv, (float *)out, B, M, P, C / 4, (const int *)nullptr)
     if (out_dtype == 1) { if (in_dtype == 0) CF_LAUNCH(1, 0); else if (in_dtype == 1) CF_LAUNCH(1, 1); else CF_LAUNCH(1, 2); }
     else                { if (in_dtype == 0) CF_LAUNCH(2, 0); else if (in_dtype == 1) CF_LAUNCH(2, 1); else CF_LAUNCH(2, 2); }
 #undef CF_LAUNCH
@@ -922,8 +996,8 @@ extern "C" int usot_rows_copy_multi_f32(void *stream, int nseg, const float *con
     return USOT_OK;
 }
 
-extern "C" int usot_rows_append_gather_f32(void *stream, const float *const *fresh, float *const *bank, float *const *picked,
-                                           const int32_t *row_len, const int32_t *idx_dev, int n_pick, int slot_pos)
+static int rows_append_gather_impl(void *stream, const float *const *fresh, float *const *bank, float *const *picked,
+                                   const int32_t *row_len, const int32_t *idx_dev, int n_pick, int slot_pos, int32_t *mem_map)
 {
     if (!fresh || !bank || !picked || !row_len || !idx_dev || n_pick < 1 || n_pick > 32 || slot_pos < 0) return USOT_EINVAL;
     RowsAG k;
@@ -940,9 +1014,23 @@ extern "C" int usot_rows_append_gather_f32(void *stream, const float *const *fre
     if (most > 0x3fffffffL) return USOT_EINVAL;
     k.n_pick = n_pick; k.slot_pos = slot_pos;
     const int blocks = (int)((most + 255) / 256 > 64 ? 64 : (most + 255) / 256);
-    hipLaunchKernelGGL(rows_append_gather_kernel, dim3(blocks, 7), dim3(256), 0, (hipStream_t)stream, k, (const int *)idx_dev);
+    if (mem_map) hipLaunchKernelGGL(rows_append_gather_dedupe_kernel, dim3(blocks, 7), dim3(256), 0, (hipStream_t)stream, k, (const int *)idx_dev, (int *)mem_map);
+    else         hipLaunchKernelGGL(rows_append_gather_kernel, dim3(blocks, 7), dim3(256), 0, (hipStream_t)stream, k, (const int *)idx_dev);
     USOT_CHECK_LAUNCH();
     return USOT_OK;
+}
+
+extern "C" int usot_rows_append_gather_f32(void *stream, const float *const *fresh, float *const *bank, float *const *picked,
+                                           const int32_t *row_len, const int32_t *idx_dev, int n_pick, int slot_pos)
+{
+    return rows_append_gather_impl(stream, fresh, bank, picked, row_len, idx_dev, n_pick, slot_pos, nullptr);
+}
+
+extern "C" int usot_rows_append_gather_dedupe_f32(void *stream, const float *const *fresh, float *const *bank, float *const *picked,
+                                                  const int32_t *row_len, const int32_t *idx_dev, int n_pick, int slot_pos, int32_t *mem_map)
+{
+    if (!mem_map || ((uintptr_t)mem_map & 3)) return USOT_EINVAL;
+    return rows_append_gather_impl(stream, fresh, bank, picked, row_len, idx_dev, n_pick, slot_pos, mem_map);
 }
 
 extern "C" int usot_thin_conv3x3_f32(void *stream, const usot_conv_desc *d, int n)

@@ -78,7 +78,10 @@ int issue(Plan *pl, hipStream_t main_stream, bool lanes, hipEvent_t *marks = nul
                 rc = usot_conv2d_batch_f32(s, tmp, op.nconv);
             }
             break;
-        case K_GDW:  rc = op.i[6] ? usot_groupdw_multi_lp(s, op.gdw, op.ngdw, op.i[6]) : usot_groupdw_multi_f32(s, op.gdw, op.ngdw); break;
+        case K_GDW:
+            rc = op.i[6] ? usot_groupdw_multi_lp(s, op.gdw, op.ngdw, op.i[6])
+                         : usot_groupdw_multi_dyn_f32(s, op.gdw, op.ngdw, (const int32_t *)op.p[0]);      // (p[0] NULL: the static launch)
+            break;
         case K_STEM:
             rc = usot_stem_conv_mu_f32(s, (const float *)op.p[0], (const float *)op.p[1], (const float *)op.p[2],
                                        (float *)op.p[3], op.i[0], op.i[1], op.i[2], op.i[3], op.i[4], op.f[1], op.f[2], op.f[3]);
@@ -89,8 +92,8 @@ int issue(Plan *pl, hipStream_t main_stream, bool lanes, hipEvent_t *marks = nul
             break;
         case K_CONF:
             rc = op.i[6] ? usot_conf_fusion_reduce_lp(s, op.p[0], op.i[5], (void *)op.p[1], op.i[0], op.i[1], op.i[2], op.i[3], op.i[6])
-                         : usot_conf_fusion_reduce_f32(s, (const float *)op.p[0], (float *)op.p[1], op.i[0], op.i[1],
-                                                       op.i[2], op.i[3]);
+                         : usot_conf_fusion_reduce_map_f32(s, (const float *)op.p[0], (float *)op.p[1], op.i[0], op.i[1],
+                                                           op.i[2], op.i[3], (const int32_t *)op.p[2]);      // (p[2] NULL: no slot map)
             break;
         case K_PRROI:
             rc = usot_prroi_pool_forward_f32(s, (const float *)op.p[0], (const float *)op.p[1], (float *)op.p[2],
@@ -169,7 +172,9 @@ int issue(Plan *pl, hipStream_t main_stream, bool lanes, hipEvent_t *marks = nul
             const float *fresh[4] = {(const float *)op.p[0], (const float *)op.p[1], (const float *)op.p[2], (const float *)op.p[3]};
             float *bank[4] = {(float *)op.l[0], (float *)op.l[1], (float *)op.l[2], (float *)op.l[3]};
             float *picked[3] = {(float *)op.l[4], (float *)op.l[5], (float *)op.l[6]};
-            rc = usot_rows_append_gather_f32(s, fresh, bank, picked, &op.i[2], (const int32_t *)op.p[4], op.i[0], op.i[1]);
+            rc = op.p[5] ? usot_rows_append_gather_dedupe_f32(s, fresh, bank, picked, &op.i[2], (const int32_t *)op.p[4], op.i[0], op.i[1],
+                                                              (int32_t *)op.p[5])
+                         : usot_rows_append_gather_f32(s, fresh, bank, picked, &op.i[2], (const int32_t *)op.p[4], op.i[0], op.i[1]);
             break;
         }
         case K_DECB:
@@ -524,6 +529,16 @@ extern "C" int usot_plan_add_rows_append_gather(void *plan, const float *const *
     return USOT_OK;
 }
 
+extern "C" int usot_plan_add_rows_append_gather_dedupe(void *plan, const float *const *fresh, float *const *bank, float *const *picked,
+                                                       const int32_t *row_len, const int32_t *idx_dev, int n_pick, int slot_pos,
+                                                       int32_t *mem_map)
+{
+    if (!mem_map || ((uintptr_t)mem_map & 3)) return USOT_EINVAL;
+    const int rc = usot_plan_add_rows_append_gather(plan, fresh, bank, picked, row_len, idx_dev, n_pick, slot_pos);
+    if (rc == USOT_OK) ((Plan *)plan)->ops.back().p[5] = mem_map;
+    return rc;
+}
+
 // lock-step multi-video tracking (csrc/multitrack.hip): the plan adders check their arguments as the eager entry points do
 extern "C" int usot_plan_add_decode_batch(void *plan, const float *cls, const float *cls_mem, const float *bbox, const double *window,
                                           double *out, int B, int S, int instance_size, int stride, float ratio, double penalty_k,
@@ -616,6 +631,13 @@ extern "C" int usot_plan_add_groupdw_multi(void *plan, const usot_groupdw_desc *
     return USOT_OK;
 }
 
+extern "C" int usot_plan_add_groupdw_multi_dyn(void *plan, const usot_groupdw_desc *d, int nseg, const int32_t *last_count)
+{
+    const int rc = usot_plan_add_groupdw_multi(plan, d, nseg);
+    if (rc == USOT_OK) ((Plan *)plan)->ops.back().p[0] = last_count;
+    return rc;
+}
+
 extern "C" int usot_plan_add_groupdw_multi_lp(void *plan, const usot_groupdw_desc *d, int nseg, int out_dtype)
 {
     if (!d || nseg < 1 || nseg > 3 || (out_dtype != 1 && out_dtype != 2)) return USOT_EINVAL;
@@ -671,6 +693,13 @@ extern "C" int usot_plan_add_conf_reduce(void *plan, const float *cv, float *out
     op->p[0] = cv; op->p[1] = out;
     op->i[0] = B; op->i[1] = M; op->i[2] = P; op->i[3] = C;
     return USOT_OK;
+}
+
+extern "C" int usot_plan_add_conf_reduce_map(void *plan, const float *cv, float *out, int B, int M, int P, int C, const int32_t *map)
+{
+    const int rc = usot_plan_add_conf_reduce(plan, cv, out, B, M, P, C);
+    if (rc == USOT_OK) ((Plan *)plan)->ops.back().p[2] = map;
+    return rc;
 }
 
 extern "C" int usot_plan_add_prroi(void *plan, const float *feat, const float *rois, float *out,

@@ -46,6 +46,8 @@ struct GdwK {
     int nseg, OH, OW, C;
     int nty, ntx;      // patch grid
     int total;         // samples over all segments
+    const int *dyn;    // strips kernel only: nullptr, or a device word with the number of samples of the LAST segment that are live in
+    int fixed;         // this launch (usot_groupdw_multi_dyn_f32): samples = fixed + *dyn, fixed = the samples of the segments before it
 };
 
 template <int RS, int CW, int WPS>
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(256, WPS) void groupdw_nhwc_kernel(const GdwK p)
         s = v / ntile;
         tile = v - s * ntile;
     }
-    if (s >= p.total) return;
+    if (s >= (p.dyn ? min(p.fixed + max(*p.dyn, 0), p.total) : p.total)) return;
     const int c = cgi * 64 + (threadIdx.x & 63);
     int sg = 0;
     while (sg + 1 < p.nseg && s >= p.seg[sg].S) { s -= p.seg[sg].S; ++sg; }
@@ -1085,7 +1087,7 @@ extern "C" int usot_groupdw_auto_variant(int total_samples, int OW)
     return groupdw_auto_mode(total_samples, OW);
 }
 
-static int groupdw_multi_impl(void *stream, const usot_groupdw_desc *d, int nseg, int out_dtype)
+static int groupdw_multi_impl(void *stream, const usot_groupdw_desc *d, int nseg, int out_dtype, const int32_t *last_count = nullptr)
 {
     const int usot_dv = usot_device_slot();        // per-device launcher state below (common.h)
     if (usot_dv < 0) return USOT_ESTATE;
@@ -1093,6 +1095,7 @@ static int groupdw_multi_impl(void *stream, const usot_groupdw_desc *d, int nseg
     static const int hk[3] = {5, 3, 5}, wk[3] = {5, 5, 3};
     GdwK p;
     p.nseg = nseg; p.OH = d[0].OH; p.OW = d[0].OW; p.C = d[0].C;
+    p.dyn = nullptr; p.fixed = 0;
     if (p.OH < 1 || p.OW < 1 || p.C <= 0 || (p.C & 63)) return USOT_EINVAL;
     int total = 0;
     for (int sidx = 0; sidx < nseg; ++sidx) {
@@ -1124,6 +1127,11 @@ static int groupdw_multi_impl(void *stream, const usot_groupdw_desc *d, int nseg
         bool once = true;
         for (int sidx = 0; sidx < nseg; ++sidx) once = once && d[sidx].x_rep == 1;
         if (once) mode = 7;
+    }
+    if (last_count) {                    // run-time sample count of the last segment: the strips kernel of a frame only
+        if (mode != 1 || out_dtype || ((uintptr_t)last_count & 3)) return USOT_EINVAL;
+        p.dyn = (const int *)last_count;
+        p.fixed = total - d[nseg - 1].S;
     }
     hipStream_t s = (hipStream_t)stream;
     if (mode != 0 && mode != 1 && mode != 2 && mode != 3 && mode != 4 && mode != 5 && mode != 6 && mode != 50 && mode != 52 && mode != 7 && mode != 8 && mode != 9) return USOT_EINVAL;
@@ -1265,6 +1273,15 @@ extern "C" int usot_groupdw_f32(void *stream, const usot_groupdw_desc *d)
 extern "C" int usot_groupdw_multi_f32(void *stream, const usot_groupdw_desc *d, int nseg)
 {
     return groupdw_multi_impl(stream, d, nseg, 0);
+}
+
+/* the same launch with the number of live samples of its LAST segment read from device memory at run time: *last_count, clamped to
+ * [0, d[nseg - 1].S].  The grid stays sized for d[nseg - 1].S samples; workgroups of the samples past the count leave at once and
+ * their outputs are not written.  The strips kernel (the variant a single frame runs) only: USOT_EINVAL where the launcher would
+ * pick, or the descriptor asks for, another variant.  last_count == NULL: usot_groupdw_multi_f32. */
+extern "C" int usot_groupdw_multi_dyn_f32(void *stream, const usot_groupdw_desc *d, int nseg, const int32_t *last_count)
+{
+    return groupdw_multi_impl(stream, d, nseg, 0, last_count);
 }
 
 /* the same launch with the OUTPUT maps stored as fp16 (out_dtype 1) or bf16 (2): d[i].out points to 16-bit elements.  fp32

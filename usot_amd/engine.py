@@ -319,7 +319,7 @@ class Builder:
 
     def conv_desc(self, name, pc, x, n, h, w, *, cout=None, act=ACT_NONE, res=None, y=None, y_cstride=0, y_coff=0,
                   act2=ACT_NONE, act_split=0, y_nchw=False, groups=1, x_gs=0, y_gs=0, w_rows=None, row0=0, tile=None,
-                  force_ks=None):
+                  force_ks=None, n_dyn=None, n_first=0):
         """Descriptor of one convolution (nothing is added to the plan yet).
         x: tensor (NHWC dense, channels == pc.cin).  Returns (desc, y, oh, ow, log, geom)."""
         cout = cout or pc.cout
@@ -365,7 +365,12 @@ class Builder:
                           y_gs=y_gs if y_gs else n * oh * ow * cout, r_gs=0,
                           ksplit=ksplit, tile=ttile, ws=ws.data_ptr() if ws is not None else None, w_frag=frag,
                           w_scale=wsc.data_ptr() + row0 * 4 if wsc is not None else None,
-                          ovf=self.ovf_word().data_ptr() if frag == 2 else None)
+                          ovf=self.ovf_word().data_ptr() if frag == 2 else None,
+                          n_dyn=n_dyn.data_ptr() if n_dyn is not None else None, n_first=n_first)
+        if n_dyn is not None:               # run-time image count (usot_conv_desc.n_dyn): producer / consumer tiles only - say so here, not at replay
+            if not hip.lib().usot_conv_tile_dyn(ttile):
+                raise hip.HipError('%s: conv tile %d takes no run-time image count (n_dyn)' % (name, ttile))
+            self.plan.keep.append(n_dyn)
         self.last_ws = ws
         self.plan.keep += [x, wbank, pc.b, wsc]
         log = (name, m, cout, k, groups, m * cout * k * groups)
@@ -1113,14 +1118,24 @@ class Builder:
         self.plan.keep += list(xs) + list(zs) + [out]
         return d
 
-    def groupdw_flush(self, descs):
+    def groupdw_flush(self, descs, last_count=None):
+        """last_count: device int32 word - the number of live samples of the LAST segment, read by the launch (usot_groupdw_multi_dyn_f32)."""
         arr = (hip.GroupDWDesc * len(descs))(*descs)
+        if last_count is not None:
+            hip.check(hip.lib().usot_plan_add_groupdw_multi_dyn(self.plan.h, arr, len(descs), hip.ptr(last_count)), 'plan_add_groupdw_multi_dyn')
+            self.plan.keep.append(last_count)
+            return
         hip.check(hip.lib().usot_plan_add_groupdw_multi(self.plan.h, arr, len(descs)), 'plan_add_groupdw_multi')
 
     # ---- a9: heads.  xf NHWC [b,hf,hf,256]; zk: 3 maps [b,hk,wk,512]; mem_nhwc [b*m,7,7,256] or None
     # `mk` may be passed when the memory-kernel encodes were already issued (on a side lane).
-    def heads(self, xf, b, hf, zk, mem_nhwc, m, mk=None, mem_lane=None):
+    # `mem_map` (Session, 'mem_dedupe'): device int32[1 + m] written by the gather in front of the heads - [0] = D, the number of
+    # DISTINCT memory rows of this frame, [1 + j] = the distinct-row index slot j uses; mk then holds D kernels, and the memory
+    # branch's GroupDW segment, Conf_Fusion's conv and its reduction run on D maps (b == 1, serial schedule).
+    def heads(self, xf, b, hf, zk, mem_nhwc, m, mk=None, mem_lane=None, mem_map=None):
         W, L = self.W, hip.lib()
+        if mem_map is not None and (b != 1 or self.lanes >= 2 or mk is None):
+            raise hip.HipError('mem_map needs the serial single-stream heads with pre-encoded memory kernels')
         es = [None] * 3
         if self.lanes < 3:                                # three encoder geometries in one launch
             eks = self.opt.get('enc_s_ksplit') or (None, None, None)
@@ -1146,7 +1161,7 @@ class Builder:
                 self.join(mem_lane, 1)
             dwm = self.buf(b * m, S, S, 256)
             segs.append(self.groupdw(es, mk, dwm, W.cls_wsm, b * m, m, S, S, 0, 256))
-        self.groupdw_flush(segs)
+        self.groupdw_flush(segs, last_count=mem_map[0:1] if mem_map is not None else None)
         gs = b * S * S * 256
         tout = [self.buf(ngroups, b, S, S, 256) for _ in range(4)]
         bbox = self.buf(b, 4, S, S)
@@ -1154,7 +1169,33 @@ class Builder:
         if has_mem and self.lanes < 2:
             # serial schedule: one 3-group launch per tower level (fewest launches)
             ts = self.opt.get('conf_tail_split')
-            if ts and b * m > ts[0]:
+            self.conf_log = None
+            if mem_map is not None:
+                # distinct maps only: ONE launch of at most four problems over distinct-map indices, each with the run-time image count
+                # mem_map[0] and its first index (usot_conv_desc.n_dyn / n_first) - the workgroups of maps >= D leave at once.  Problems
+                # = runs of equal split-K factors of 'conf_map_split' (one factor per map), cut behind map 3 as well (steady state
+                # D = 4): the problems that are empty in steady state then own the highest block ids of the launch
+                lay = tuple(self.opt.get('conf_map_split') or (1,) * m)
+                if len(lay) != m:
+                    raise hip.HipError('conf_map_split has %d factors for %d memory maps' % (len(lay), m))
+                cuts = sorted({0, m} | {i for i in range(1, m) if lay[i] != lay[i - 1]} | ({4} if m > 4 else set()))
+                if len(cuts) - 1 > 4:
+                    raise hip.HipError('conf_map_split %r needs %d problems; a launch takes four' % (lay, len(cuts) - 1))
+                skew = False
+                cv = self.buf(m, S, S, 512)
+                kw = dict(act=ACT_CONF, act2=ACT_RELU, act_split=256, n_dyn=mem_map[0:1])
+                full_tile = self.tuning.get((m * S * S, 512, W.conf.kh * W.conf.kw * W.conf.cin, 1), (0, 1))[0]
+                if not L.usot_conv_tile_dyn(full_tile):
+                    # an untuned queue length (or a table that routes the shape elsewhere): the 32 x 64 producer / consumer tile every
+                    # tuned length of this convolution runs on - the batch default (a v2 tile) takes no run-time count
+                    full_tile = 55
+                nlog = len(self.log)
+                self.conv_batch([('conf_fusion[%d:%d]' % (a, e), W.conf, dwm[a:e], e - a, S, S,
+                                  dict(y=cv[a:e], force_ks=lay[a], n_first=a, **kw)) for a, e in zip(cuts[:-1], cuts[1:])],
+                                lead_tile=full_tile)
+                if len(self.log) == nlog + 1:           # what Session.log restates per frame: (entry, pixels per map, Cout, K)
+                    self.conf_log = (nlog, S * S, 512, W.conf.kh * W.conf.kw * W.conf.cin)
+            elif ts and b * m > ts[0]:
                 # whole-chip rounds: the last `tail` memory maps run split-K in the same launch (see DEFAULT_OPTIONS)
                 tail, ks = ts
                 head_n = b * m - tail
@@ -1175,8 +1216,12 @@ class Builder:
             else:
                 skew = False
                 cv, _, _ = self.conv('conf_fusion', W.conf, dwm, b * m, S, S, act=ACT_CONF, act2=ACT_RELU, act_split=256)
-            hip.check(L.usot_plan_add_conf_reduce(self.plan.h, hip.ptr(cv), hip.ptr(tin[2]), b, m, S * S, 256),
-                      'plan_add_conf_reduce')
+            if mem_map is not None:
+                hip.check(L.usot_plan_add_conf_reduce_map(self.plan.h, hip.ptr(cv), hip.ptr(tin[2]), b, m, S * S, 256, hip.ptr(mem_map[1:])),
+                          'plan_add_conf_reduce_map')
+            else:
+                hip.check(L.usot_plan_add_conf_reduce(self.plan.h, hip.ptr(cv), hip.ptr(tin[2]), b, m, S * S, 256),
+                          'plan_add_conf_reduce')
             cur = tin
             if skew:
                 # the memory tower runs one level behind: [tower_i(mem) | tower_{i+1}(reg, cls)] per launch, tower_3(mem) alone
@@ -1415,6 +1460,16 @@ DEFAULT_OPTIONS = {
     # rounds; None = one unsplit convolution.  Same-process A/B of the frame graph (scripts/tail_split_ab.py): unsplit 866 us,
     # (1, 2) 851.5, (1, 7) 856, (2, 3) 856, (1, 3) 870
     'conf_tail_split': (1, 2),
+    # Session ('defer_append' = 2): the frame's memory branch runs on the DISTINCT memory rows only.  The reference's index formula
+    # (usot_tracker.py:237-242, kept literally in tracker.select_memory) picks [init, flip, 2 + best, 2 + last x 4] once five features
+    # are stored: 4 distinct rows of 7 (3 on the first frame), and GroupDW's memory segment, Conf_Fusion's conv and the gather worked
+    # on 7.  The gather kernel dedupes on the device and publishes D + the slot map (usot_rows_append_gather_dedupe_f32); the
+    # launches behind it are captured for 7 maps and read D at run time (workgroups with nothing to do leave at once; nobody waits
+    # for anybody).  False: the static graph of before, bit for bit
+    'mem_dedupe': True,
+    # ... and the split-K factor of each of Conf_Fusion's maps then (None = all unsplit; a tuple of mem_queue_size factors, at most
+    # four runs of equal factors counting the cut behind map 3).  'conf_tail_split' keeps its meaning for the static paths
+    'conf_map_split': None,
     # per-geometry split-K factors of the three search-side encoder convs that share one launch (None = the tuned table)
     'enc_s_ksplit': None,
     # Session.collect(): wall-clock budget of the result-tag spin before it falls back to 50 us sleeps
@@ -1457,6 +1512,8 @@ ENV_SWITCHES = {      # environment variable -> (option, parser)
     'USOT_FUSED_F32_SLICED': ('fused_f32_sliced', lambda v: v == '1'),
     'USOT_SPIN_SECONDS': ('spin_seconds', float),
     'USOT_SPLIT16_F32': ('split16_f32', lambda v: v == '1'),
+    'USOT_MEM_DEDUPE': ('mem_dedupe', lambda v: v == '1'),
+    'USOT_CONF_MAP_SPLIT': ('conf_map_split', lambda v: tuple(int(t) for t in v.split(',') if t) or None),      # '' = unsplit, '1,1,1,2,1,1,1'
     'USOT_DEFER_APPEND': ('defer_append', int),
     'USOT_DEFER_APPEND_ENC_KS': ('defer_append_enc_ks', int),
     'USOT_CONV_PW_LP': ('conv_pw_lp', lambda v: tuple(int(t) for t in v.split(',') if t)),      # '' = off, '256', '256,128'
@@ -1491,6 +1548,9 @@ def merged_options(overrides=None):
     if ts is not None and not (isinstance(ts, (tuple, list)) and len(ts) == 2 and all(isinstance(v, int) and not isinstance(v, bool) for v in ts)
                                and ts[0] >= 1 and ts[1] >= 2):
         raise hip.HipError('conf_tail_split must be None or (tail maps >= 1, ksplit >= 2); got %r' % (ts,))
+    lay = opt.get('conf_map_split')
+    if lay is not None and not (isinstance(lay, (tuple, list)) and lay and all(isinstance(v, int) and not isinstance(v, bool) and v >= 1 for v in lay)):
+        raise hip.HipError('conf_map_split must be None or a tuple of split-K factors >= 1, one per memory map; got %r' % (lay,))
     return opt
 
 
@@ -1841,6 +1901,10 @@ class Session:
         if self.defer == 2 and nq > 32:             # usot_rows_append_gather_f32 takes up to 32 picked rows: longer queues append in-frame
             self.defer = 0
         self._pending, self._prev_slot = False, self.cap - 1
+        # 'mem_dedupe': [0] = D, the distinct rows among this frame's picks, [1 + j] = the distinct-row index of slot j - written by the
+        # gather, read by GroupDW, Conf_Fusion's conv and the reduction.  Starts as the identity (every row distinct = the static frame)
+        self.mem_map = torch.tensor([nq] + list(range(nq)), dtype=torch.int32, device=e.device)
+        self.dedupe = self.defer == 2 and bool(e.opt['mem_dedupe'])
         if self.defer == 2:
             # 'defer_append' = 2 (round 6): the same deferral WITHOUT a side branch.  The previous frame's three encoder
             # convolutions ride in the launch of layer2's shortcut conv (Builder.piggyback), and ONE kernel in front of the heads
@@ -1856,10 +1920,14 @@ class Session:
                 new_enc = bld.encode_kernel(self.feat, 1, 256, 'mem')
             fresh, banks = [self.feat] + new_enc, [self.bank] + self.bank_enc
             rl = [int(b[0].numel()) for b in banks]
-            hip.check(L.usot_plan_add_rows_append_gather(
-                pl.h, (C.c_void_p * 4)(*[t.data_ptr() for t in fresh]), (C.c_void_p * 4)(*[t.data_ptr() for t in banks]),
-                (C.c_void_p * 3)(*[t.data_ptr() for t in mk]), (C.c_int32 * 4)(*rl), hip.ptr(idx_dev), nq, nq + 3),
-                'plan_add_rows_append_gather')
+            ag = (pl.h, (C.c_void_p * 4)(*[t.data_ptr() for t in fresh]), (C.c_void_p * 4)(*[t.data_ptr() for t in banks]),
+                  (C.c_void_p * 3)(*[t.data_ptr() for t in mk]), (C.c_int32 * 4)(*rl), hip.ptr(idx_dev), nq, nq + 3)
+            if self.dedupe:
+                for t in mk:
+                    t.zero_()       # rows >= D of the picked kernels are never written, and never read: defined all the same
+                hip.check(L.usot_plan_add_rows_append_gather_dedupe(*ag, hip.ptr(self.mem_map)), 'plan_add_rows_append_gather_dedupe')
+            else:
+                hip.check(L.usot_plan_add_rows_append_gather(*ag), 'plan_add_rows_append_gather')
         elif self.defer:
             pl.fork(3)
             new_enc = bld.encode_kernel(self.feat, 1, 256, 'mem')       # the PREVIOUS frame's pooled feature
@@ -1876,7 +1944,8 @@ class Session:
             # slot_dev[0] = the append row, slot_dev[1:3] = the crop's address: both stashed from the control block by the
             # gather above (the first kernel of the frame)
             xf, hf = bld.backbone(self.x, 1, self.size, need_stem=False, xptr_dev=self.slot_dev[1:3])
-        bbox, cls2, S = bld.heads(xf, 1, hf, self.zk, self.mem_in, nq, mk=mk, mem_lane=None if self.defer else 2)
+        bbox, cls2, S = bld.heads(xf, 1, hf, self.zk, self.mem_in, nq, mk=mk, mem_lane=None if self.defer else 2,
+                                  mem_map=self.mem_map if self.dedupe else None)
         assert S == self.S
         p = self.p
         hip.check(L.usot_plan_add_decode(pl.h, hip.ptr(cls2[0]), hip.ptr(cls2[1]), hip.ptr(bbox), hip.ptr(self.window),
@@ -1897,10 +1966,11 @@ class Session:
             self._rows_multi(fb.plan, [self.feat] + fenc, self._flush_idx, [self.bank] + self.bank_enc, 1, scatter=1)
             fb.plan.keep += fenc + [self.feat, self._flush_idx, self.bank] + self.bank_enc
             self._flush_plan = fb.plan
-        pl.keep += mk + new_enc + self.bank_enc + [self.slot_dev]
+        pl.keep += mk + new_enc + self.bank_enc + [self.slot_dev, self.mem_map]
         pl.keep += [self.bank, self.ctl, self.window, self.out8, tsz_dev, idx_dev] + self.zk
-        self.xf, self.cls2, self.bbox, self.plan, self.log = xf, cls2, bbox, pl, bld.log
-        self.f32_bytes = bld.f32_bytes
+        self.xf, self.cls2, self.bbox, self.plan, self._log = xf, cls2, bbox, pl, bld.log
+        self._f32_bytes = bld.f32_bytes
+        self._conf_log = getattr(bld, 'conf_log', None) if self.dedupe else None
         # split-fp16 range word of this frame graph (Builder.ovf): its address travels in the control block, the decode kernel
         # publishes its value as out[9] with the results and clears it (csrc/head_ops.hip); 0 = no split-fp16 launch in the graph
         self._ovf = bld.ovf
@@ -1913,6 +1983,22 @@ class Session:
         torch.cuda.current_stream().synchronize()
         self.feat.zero_()                   # the warm-up replay pooled a feature of the zero crop: not a pending append
         torch.cuda.current_stream().synchronize()
+
+    def _stated(self, which):
+        """log / f32_bytes as the frame last submitted RAN them: with 'mem_dedupe' Conf_Fusion's launch is captured for mem_queue_size
+        maps and computes the distinct rows of the control block last written.  Worked out here, when somebody asks (bench.py's
+        roofline), not per frame on the submit path."""
+        log, nbytes = list(self._log), list(self._f32_bytes)
+        if self._conf_log is not None:
+            i, pix, cout, k = self._conf_log
+            d = len(set(int(r) for r in self._ctl_i32[:self.nq]))
+            w = self.e.W.conf
+            log[i] = (log[i][0], d * pix, cout, k, 1, d * pix * cout * k)
+            nbytes[i] = 4 * (d * pix * (w.cin + cout) + cout * k + cout)          # (Builder._conv_bytes on d maps)
+        return log if which == 'log' else nbytes
+
+    log = property(lambda self: self._stated('log'))
+    f32_bytes = property(lambda self: self._stated('f32_bytes'))
 
     def flush(self):
         """'defer_append': append the last frame's pooled feature to the bank NOW (it otherwise happens inside the next frame's

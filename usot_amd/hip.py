@@ -33,6 +33,8 @@ EXPORTS = (
     'usot_decode_batch_f32', 'usot_plan_add_decode_batch', 'usot_rows_append_gather_batch_f32', 'usot_plan_add_rows_append_gather_batch',
     'usot_crop_resize_batch_u8_f32', 'usot_plan_add_crop_resize_batch',
     'usot_xcorr_depthwise_bwd_x_f32', 'usot_xcorr_depthwise_bwd_k_f32',
+    'usot_rows_append_gather_dedupe_f32', 'usot_plan_add_rows_append_gather_dedupe', 'usot_groupdw_multi_dyn_f32',
+    'usot_plan_add_groupdw_multi_dyn', 'usot_conf_fusion_reduce_map_f32', 'usot_plan_add_conf_reduce_map', 'usot_conv_tile_dyn',
 )
 
 
@@ -54,7 +56,8 @@ class ConvDesc(C.Structure):
                 ('x_gs', C.c_int64), ('w_gs', C.c_int64), ('b_gs', C.c_int64), ('y_gs', C.c_int64),
                 ('r_gs', C.c_int64),
                 ('ksplit', C.c_int32), ('tile', C.c_int32), ('w_frag', C.c_int32), ('defer', C.c_int32),
-                ('w_scale', C.c_void_p), ('x_split', C.c_int32), ('y_split', C.c_int32), ('ovf', C.c_void_p)]
+                ('w_scale', C.c_void_p), ('x_split', C.c_int32), ('y_split', C.c_int32), ('ovf', C.c_void_p),
+                ('n_dyn', C.c_void_p), ('n_first', C.c_int32)]
 
 
 class GroupDWDesc(C.Structure):
@@ -164,6 +167,13 @@ def lib():
         L.usot_crop_resize_u8_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 9
         L.usot_decode_batch_f32.argtypes = [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float] + [C.c_double] * 2 + [C.c_void_p] * 2
         L.usot_plan_add_decode_batch.argtypes = [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float] + [C.c_double] * 2 + [C.c_void_p] * 2
+        L.usot_rows_append_gather_dedupe_f32.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
+        L.usot_plan_add_rows_append_gather_dedupe.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
+        L.usot_groupdw_multi_dyn_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.usot_plan_add_groupdw_multi_dyn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.usot_conf_fusion_reduce_map_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]
+        L.usot_plan_add_conf_reduce_map.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]
+        L.usot_conv_tile_dyn.argtypes = [C.c_int]
         L.usot_rows_append_gather_batch_f32.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3
         L.usot_plan_add_rows_append_gather_batch.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3
         L.usot_crop_resize_batch_u8_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 2
@@ -410,7 +420,7 @@ def split16_pack(w):
 def conv_desc(x, w, bias, y, *, N, H, W, Cin, OH, OW, Cout, KH, KW, stride=1, pad=(0, 0), dil=(1, 1),
               res=None, act=ACT_NONE, act2=ACT_NONE, act_split=0, y_cstride=0, y_coff=0,
               res_cstride=0, res_coff=0, y_nchw=0, groups=1, x_gs=0, w_gs=0, b_gs=0, y_gs=0, r_gs=0,
-              ksplit=1, tile=0, ws=None, w_frag=0, defer=0, w_scale=None, x_split=0, y_split=0, ovf=None):
+              ksplit=1, tile=0, ws=None, w_frag=0, defer=0, w_scale=None, x_split=0, y_split=0, ovf=None, n_dyn=None, n_first=0):
     d = ConvDesc()
     d.x, d.w, d.bias, d.res, d.y, d.ws = (x, w, bias or None, res or None, y, ws or None)
     d.N, d.H, d.W, d.Cin, d.OH, d.OW, d.Cout = N, H, W, Cin, OH, OW, Cout
@@ -424,6 +434,7 @@ def conv_desc(x, w, bias, y, *, N, H, W, Cin, OH, OW, Cout, KH, KW, stride=1, pa
     d.w_scale = w_scale or None
     d.x_split, d.y_split = int(x_split), int(y_split)
     d.ovf = ovf or None          # split-fp16 tiles: the sticky "a finished sum was not finite" word (usot_conv_desc.ovf)
+    d.n_dyn, d.n_first = n_dyn or None, int(n_first)      # run-time image count (usot_conv_desc.n_dyn): a device address, or off
     return d
 
 
