@@ -399,6 +399,54 @@ int usot_xcorr_depthwise_bwd_x_f32(void *stream, const float *dout, const float 
 int usot_xcorr_depthwise_bwd_k_f32(void *stream, const float *dout, const float *x, float *dk,
                                    int P, int Hx, int Wx, int Hk, int Wk, float scale);
 
+/* ---- gradients of the fp32 convolution (csrc/conv_grad.hip).  The convolution is the one usot_conv_desc describes, groups = 1,
+ * no residual, no activation, with the forward's layouts:
+ *   x    NHWC  [N][H][W][Cin], Cin % 32 == 0
+ *   w    packed [Cout][K], K = KH*KW*Cin, k = (kh*KW + kw)*Cin + ci
+ *   dy   dense NHWC [N][OH][OW][Cout], the gradient of the convolution's output; m = (n*OH + oh)*OW + ow, M = N*OH*OW
+ *   dw[co][k]       = sum_m dy[m][co] * x[n][oh*stride - pad_h + kh*dil_h][ow*stride - pad_w + kw*dil_w][ci]   (taps outside x are 0)
+ *   db[co]          = sum_m dy[m][co]
+ *   dx[n][h][w][ci] = sum over (co, kh, kw) and the output pixels whose tap (kh, kw) is x[n][h][w] of dy[m][co] * w[co][k]
+ * Every pointer a launch uses must be 16-byte aligned.  Outputs are written once per element with plain stores: no atomics,
+ * nothing has to be cleared, and every sum has an order fixed by the code, so equal inputs (and an equal psplit) give equal bits.
+ *
+ * usot_conv2d_wgrad_f32 (needs x, dy, dw; db NULL = not computed) runs on v_mfma_f32_16x16x4_f32 with the pixel index as the
+ *   reduction axis.  A workgroup owns a tile of dw - *bco channels x *bk filter elements (usot_conv2d_wgrad_geometry) - and one of
+ *   `psplit` slices of the pixels, slice s = [M*s/psplit, M*(s+1)/psplit), which it walks in steps of *chunk pixels.
+ *   Summation order of one element: the pixels of a step ascending in one fmaf chain that starts at 0; steps ascending, each
+ *   added to the slice's running total; then, with psplit > 1, the slices ascending (a second launch that reads the workspace).
+ *   db: pixels of a step ascending, steps ascending, slices ascending.
+ *   psplit 0 = the launcher's choice, usot_conv2d_wgrad_psplit(d): about four workgroups per compute unit of the current device,
+ *   no slice shorter than two steps, at most 32.  psplit > M is an error.
+ *   ws: usot_conv2d_wgrad_ws_floats(d) floats = psplit*Cout*(K + 1) - the slabs [psplit][Cout][K], then [psplit][Cout] partial
+ *   sums of db - or 0 (ws may be NULL) when the split is 1.  Its contents before the launch do not matter.
+ * usot_conv2d_dgrad_f32 (needs dy, w, dx) has two routes; usot_conv2d_dgrad_route(d) names the one a launch of d takes.
+ *   Route A (1): stride 1, Cout % 32 == 0, pad <= dil*(K-1) in both directions and wt != NULL.  dx is then the forward convolution
+ *   of dy with the bank rotated by 180 degrees and transposed, wt[ci][(kh*KW + kw)*Cout + co] = w[co][((KH-1-kh)*KW + KW-1-kw)*Cin + ci]
+ *   (usot_conv_pack_dgrad_f32 writes it), at padding dil*(K-1) - pad: the launch IS usot_conv2d_f32 on (dy, wt), heuristic tile,
+ *   its summation order.  route = 0 takes route A when it is open, and route B when it is not or when usot_conv2d_f32 answers
+ *   USOT_EINVAL for that descriptor; route = 1 insists (USOT_EINVAL when closed); route = 2 forces route B.
+ *   Route B (2): any stride and Cout; one thread per four channels of a dx pixel; per tap and block of 64 output channels an fmaf
+ *   chain over co ascending, the chains added in (kh, kw, block) order.
+ * Both launchers answer USOT_EINVAL, before they touch the device, for: a NULL pointer they need, a negative N, any other size
+ * (H, W, Cin, OH, OW, Cout, KH, KW, stride, dil) below 1, a negative pad, Cin % 32 != 0, OH / OW that are not the convolution's,
+ * psplit < 0 or > M, ws == NULL with a split above 1, a misaligned pointer.  N == 0 is a no-op that returns 0.  The host-only
+ * queries answer USOT_EINVAL for a descriptor whose geometry the launchers would reject. */
+typedef struct usot_conv_grad_desc {
+    const float *x, *w, *wt, *dy;   /* wt: rotated bank for route A, or NULL */
+    float *dx, *dw, *db, *ws;       /* NULL output = not wanted */
+    int32_t N, H, W, Cin, OH, OW, Cout, KH, KW, stride, pad_h, pad_w, dil_h, dil_w;
+    int32_t psplit;                 /* 0 = launcher's choice */
+    int32_t route;                  /* dgrad: 0 = auto, 1 = force route A (USOT_EINVAL if not eligible), 2 = force route B */
+} usot_conv_grad_desc;
+int     usot_conv2d_wgrad_f32(void *stream, const usot_conv_grad_desc *d);       /* dw, db */
+int     usot_conv2d_dgrad_f32(void *stream, const usot_conv_grad_desc *d);       /* dx */
+int64_t usot_conv2d_wgrad_ws_floats(const usot_conv_grad_desc *d);               /* host only; for psplit = 0 the launcher's own choice */
+int     usot_conv2d_wgrad_psplit(const usot_conv_grad_desc *d);                  /* host only: the split a psplit = 0 launch takes */
+int     usot_conv2d_wgrad_geometry(int *bco, int *bk, int *chunk);               /* host only: Cout block, k block, pixels staged per step */
+int     usot_conv_pack_dgrad_f32(void *stream, const float *w, float *wt, int Cout, int Cin, int KH, int KW);
+int     usot_conv2d_dgrad_route(const usot_conv_grad_desc *d);                   /* host only: 1 = route A, 2 = route B */
+
 /* ---- fused GroupDW on NHWC (connect.py:86-102): three depthwise xcorrs and the
  * softmax(weight)-weighted sum in one pass, no intermediate maps.
  *   branch b: x_b NHWC [XS][OH+hk_b-1][OW+wk_b-1] (pixel stride x_cs, channel offset x_co)

@@ -1,8 +1,9 @@
-"""torch.autograd bindings of the native depthwise cross-correlation (reference lib/models/connect.py:86-102,147-157).
+"""torch.autograd bindings of the native depthwise cross-correlation (reference lib/models/connect.py:86-102,147-157) and of
+the fp32 convolution (every nn.Conv2d of connect.py).
 
-Forward values are `usot_amd.hip.xcorr_depthwise`'s, bit for bit; the gradients come from the two kernels of
-csrc/xcorr_grad.hip.  First-order gradients only, fp32 only, device tensors only (no CPU implementation: CPU
-tensors raise `hip.HipError`).
+Forward values are `usot_amd.hip.xcorr_depthwise`'s and `usot_amd.hip.conv2d`'s, bit for bit; the gradients come from the
+kernels of csrc/xcorr_grad.hip and csrc/conv_grad.hip.  First-order gradients only, fp32 only, device tensors only (no CPU
+implementation: CPU tensors raise `hip.HipError`).
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -100,3 +101,64 @@ def groupdw(z, x, weight):
     if _wants_grad(weight, *zs, *xs):
         return GroupDWFunction.apply(weight, *zs, *xs)
     return _groupdw_forward(zs, xs, weight)[0]
+
+
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+def _pack_oihw(weight):
+    """OIHW -> the packed bank [Cout][KH*KW*Cin] of usot_conv_desc (k = (kh*KW + kw)*Cin + ci)"""
+    return weight.permute(0, 2, 3, 1).reshape(weight.shape[0], -1).contiguous()
+
+
+def _conv2d_forward(x, weight, bias, stride, pad, dil, relu):
+    """(x NHWC, packed bank, y NHWC): `hip.conv2d` on the heuristic tile"""
+    xh = hip.to_nhwc(x).contiguous()
+    wp = _pack_oihw(weight)
+    y = hip.conv2d(xh, wp, bias, KH=weight.shape[2], KW=weight.shape[3], stride=stride, pad=pad, dil=dil,
+                   act=hip.ACT_RELU if relu else hip.ACT_NONE)
+    return xh, wp, y
+
+
+class Conv2dFunction(torch.autograd.Function):
+    """y = [relu](conv2d(x, weight) + bias) on NCHW tensors and an OIHW weight; the kernels work on NHWC maps and the packed
+    bank, which is what backward keeps."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, pad, dil, relu):
+        xh, wp, y = _conv2d_forward(x.detach(), weight.detach(), None if bias is None else bias.detach(), stride, pad, dil, relu)
+        ctx.geo = (tuple(weight.shape), stride, pad, dil, relu)
+        ctx.save_for_backward(xh, wp, y if relu else None)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        xh, wp, y = ctx.saved_tensors
+        (cout, cin, kh, kw), stride, pad, dil, relu = ctx.geo
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        dy = hip.to_nhwc(dout)
+        dy = dy * (y > 0) if relu else dy.contiguous()
+        dx = dw = db = None
+        if need_x:
+            dx = hip.conv2d_backward_x(dy, wp, xh.shape, KH=kh, KW=kw, stride=stride, pad=pad, dil=dil).permute(0, 3, 1, 2)
+        if need_w or need_b:
+            dwp, db = hip.conv2d_backward_w(xh, dy, KH=kh, KW=kw, stride=stride, pad=pad, dil=dil, bias=need_b)
+            if need_w:
+                dw = dwp.view(cout, kh, kw, cin).permute(0, 3, 1, 2).contiguous()
+        return dx, dw, db, None, None, None, None
+
+
+def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, relu=False):
+    """Differentiable `F.conv2d` (groups = 1, one stride for both directions, Cin % 32 == 0) on NCHW device tensors and an OIHW
+    weight, optionally with the forward's fused ReLU.  The result is NCHW-shaped over channels-last memory."""
+    hip._dev(x), hip._dev(weight)
+    if bias is not None:
+        hip._dev(bias)
+    if x.dim() != 4 or weight.dim() != 4 or x.shape[1] != weight.shape[1]:
+        raise hip.HipError('conv2d: input %s and weight %s do not fit' % (tuple(x.shape), tuple(weight.shape)))
+    pad, dil = _pair(padding), _pair(dilation)
+    if _wants_grad(x, weight, bias):
+        return Conv2dFunction.apply(x, weight, bias, int(stride), pad, dil, bool(relu))
+    return _conv2d_forward(x, weight, bias, int(stride), pad, dil, bool(relu))[2].permute(0, 3, 1, 2)

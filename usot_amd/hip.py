@@ -35,6 +35,8 @@ EXPORTS = (
     'usot_xcorr_depthwise_bwd_x_f32', 'usot_xcorr_depthwise_bwd_k_f32',
     'usot_rows_append_gather_dedupe_f32', 'usot_plan_add_rows_append_gather_dedupe', 'usot_groupdw_multi_dyn_f32',
     'usot_plan_add_groupdw_multi_dyn', 'usot_conf_fusion_reduce_map_f32', 'usot_plan_add_conf_reduce_map', 'usot_conv_tile_dyn',
+    'usot_conv2d_wgrad_f32', 'usot_conv2d_dgrad_f32', 'usot_conv2d_wgrad_ws_floats', 'usot_conv2d_wgrad_psplit', 'usot_conv2d_wgrad_geometry',
+    'usot_conv_pack_dgrad_f32', 'usot_conv2d_dgrad_route',
 )
 
 
@@ -58,6 +60,17 @@ class ConvDesc(C.Structure):
                 ('ksplit', C.c_int32), ('tile', C.c_int32), ('w_frag', C.c_int32), ('defer', C.c_int32),
                 ('w_scale', C.c_void_p), ('x_split', C.c_int32), ('y_split', C.c_int32), ('ovf', C.c_void_p),
                 ('n_dyn', C.c_void_p), ('n_first', C.c_int32)]
+
+
+class GradDesc(C.Structure):
+    """usot_conv_grad_desc"""
+    _fields_ = [('x', C.c_void_p), ('w', C.c_void_p), ('wt', C.c_void_p), ('dy', C.c_void_p),
+                ('dx', C.c_void_p), ('dw', C.c_void_p), ('db', C.c_void_p), ('ws', C.c_void_p),
+                ('N', C.c_int32), ('H', C.c_int32), ('W', C.c_int32), ('Cin', C.c_int32),
+                ('OH', C.c_int32), ('OW', C.c_int32), ('Cout', C.c_int32),
+                ('KH', C.c_int32), ('KW', C.c_int32), ('stride', C.c_int32),
+                ('pad_h', C.c_int32), ('pad_w', C.c_int32), ('dil_h', C.c_int32), ('dil_w', C.c_int32),
+                ('psplit', C.c_int32), ('route', C.c_int32)]
 
 
 class GroupDWDesc(C.Structure):
@@ -231,6 +244,13 @@ def lib():
         L.usot_xcorr_depthwise_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5
         L.usot_xcorr_depthwise_bwd_x_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float]
         L.usot_xcorr_depthwise_bwd_k_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float]
+        for name in ('usot_conv2d_wgrad_f32', 'usot_conv2d_dgrad_f32'):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+        for name in ('usot_conv2d_wgrad_ws_floats', 'usot_conv2d_wgrad_psplit', 'usot_conv2d_dgrad_route'):
+            getattr(L, name).argtypes = [C.c_void_p]
+        L.usot_conv2d_wgrad_ws_floats.restype = C.c_int64
+        L.usot_conv2d_wgrad_geometry.argtypes = [C.POINTER(C.c_int)] * 3
+        L.usot_conv_pack_dgrad_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4
         L.usot_conf_fusion_reduce_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4
         L.usot_prroi_pool_forward_f32.argtypes = ([C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_float]
                                                   + [C.c_int64] * 8)
@@ -579,6 +599,85 @@ def xcorr_depthwise_backward_k(dout, x, kernel_shape, scale=1.0):
     check(lib().usot_xcorr_depthwise_bwd_k_f32(stream(), ptr(d), ptr(xs), ptr(dk), b * c, hx, wx, hk, wk, float(scale)),
           'usot_xcorr_depthwise_bwd_k_f32')
     return dk
+
+
+def grad_desc(*, N, H, W, Cin, Cout, KH, KW, stride=1, pad=(0, 0), dil=(1, 1), x=None, w=None, wt=None, dy=None, dx=None,
+              dw=None, db=None, ws=None, psplit=0, route=0):
+    """usot_conv_grad_desc of a convolution's geometry; pointers are addresses (or None); OH / OW are the convolution's."""
+    d = GradDesc()
+    d.x, d.w, d.wt, d.dy, d.dx, d.dw, d.db, d.ws = (v or None for v in (x, w, wt, dy, dx, dw, db, ws))
+    d.N, d.H, d.W, d.Cin, d.Cout, d.KH, d.KW, d.stride = N, H, W, Cin, Cout, KH, KW, stride
+    d.pad_h, d.pad_w, d.dil_h, d.dil_w = pad[0], pad[1], dil[0], dil[1]
+    d.OH = (H + 2 * pad[0] - dil[0] * (KH - 1) - 1) // max(stride, 1) + 1
+    d.OW = (W + 2 * pad[1] - dil[1] * (KW - 1) - 1) // max(stride, 1) + 1
+    d.psplit, d.route = psplit, route
+    return d
+
+
+def wgrad_geometry():
+    """(Cout block, k block, pixels staged per step) of the weight-gradient kernel"""
+    v = [C.c_int(0) for _ in range(3)]
+    check(lib().usot_conv2d_wgrad_geometry(*[C.byref(i) for i in v]), 'usot_conv2d_wgrad_geometry')
+    return tuple(i.value for i in v)
+
+
+def conv2d_backward_w(x, dy, *, KH, KW, stride=1, pad=(0, 0), dil=(1, 1), bias=False, psplit=0):
+    """Gradient of `conv2d` w.r.t. its packed filter bank (and its bias): x NHWC [N,H,W,Cin], dy NHWC [N,OH,OW,Cout] dense
+    -> (dw [Cout, KH*KW*Cin], db [Cout] or None).  psplit: pixel slices (0 = the launcher's choice, usot_conv_grad_desc)."""
+    _dev(x), _dev(dy)
+    if x.dim() != 4 or dy.dim() != 4 or not x.is_contiguous() or not dy.is_contiguous():
+        raise HipError('conv2d_backward_w: dense NHWC tensors expected')
+    N, H, W_, Cin = x.shape
+    Cout = dy.shape[3]
+    d = grad_desc(N=N, H=H, W=W_, Cin=Cin, Cout=Cout, KH=KH, KW=KW, stride=stride, pad=pad, dil=dil, psplit=psplit)
+    if tuple(dy.shape) != (N, d.OH, d.OW, Cout):
+        raise HipError('conv2d_backward_w: grad_output %s does not belong to input %s (expected %s)'
+                       % (tuple(dy.shape), tuple(x.shape), (N, d.OH, d.OW, Cout)))
+    K = KH * KW * Cin
+    dw = torch.empty((Cout, K), device=x.device, dtype=torch.float32)
+    db = torch.empty((Cout,), device=x.device, dtype=torch.float32) if bias else None
+    need = lib().usot_conv2d_wgrad_ws_floats(C.byref(d))
+    if need < 0:
+        check(int(need), 'usot_conv2d_wgrad_ws_floats')
+    ws = torch.empty((need,), device=x.device, dtype=torch.float32) if need else None
+    d.x, d.dy, d.dw, d.db, d.ws = x.data_ptr(), dy.data_ptr(), dw.data_ptr(), db.data_ptr() if bias else None, \
+        ws.data_ptr() if ws is not None else None
+    check(lib().usot_conv2d_wgrad_f32(stream(), C.byref(d)), 'usot_conv2d_wgrad_f32')
+    return dw, db
+
+
+def pack_dgrad(w, Cin, KH, KW):
+    """Packed bank w [Cout, KH*KW*Cin] -> the rotated, transposed bank wt [Cin, KH*KW*Cout] of the data gradient's route A."""
+    _dev(w)
+    Cout = w.shape[0]
+    if w.dim() != 2 or w.shape[1] != KH * KW * Cin or not w.is_contiguous():
+        raise HipError('pack_dgrad: bank %s is not [Cout][%d*%d*%d]' % (tuple(w.shape), KH, KW, Cin))
+    wt = torch.empty((Cin, KH * KW * Cout), device=w.device, dtype=torch.float32)
+    check(lib().usot_conv_pack_dgrad_f32(stream(), ptr(w), ptr(wt), Cout, Cin, KH, KW), 'usot_conv_pack_dgrad_f32')
+    return wt
+
+
+def conv2d_backward_x(dy, w, x_shape, *, KH, KW, stride=1, pad=(0, 0), dil=(1, 1), route=0):
+    """Gradient of `conv2d` w.r.t. its input: dy NHWC [N,OH,OW,Cout] dense, w packed [Cout, KH*KW*Cin] -> dx of shape
+    `x_shape` ([N,H,W,Cin]).  route: 0 = auto, 1 = the forward kernels on the rotated bank, 2 = the direct kernel."""
+    _dev(dy), _dev(w)
+    N, H, W_, Cin = (int(v) for v in x_shape)
+    if dy.dim() != 4 or w.dim() != 2 or not dy.is_contiguous() or not w.is_contiguous():
+        raise HipError('conv2d_backward_x: dense tensors expected')
+    Cout = w.shape[0]
+    d = grad_desc(N=N, H=H, W=W_, Cin=Cin, Cout=Cout, KH=KH, KW=KW, stride=stride, pad=pad, dil=dil, route=route)
+    if w.shape[1] != KH * KW * Cin or tuple(dy.shape) != (N, d.OH, d.OW, Cout):
+        raise HipError('conv2d_backward_x: grad_output %s / bank %s do not belong to input %s'
+                       % (tuple(dy.shape), tuple(w.shape), (N, H, W_, Cin)))
+    d.dy, d.w, d.wt = dy.data_ptr(), w.data_ptr(), 16          # wt: any address, for the route query
+    r = lib().usot_conv2d_dgrad_route(C.byref(d)) if route != 2 else 2
+    if r < 0:
+        check(r, 'usot_conv2d_dgrad_route')
+    wt = pack_dgrad(w, Cin, KH, KW) if r == 1 else None
+    dx = torch.empty((N, H, W_, Cin), device=dy.device, dtype=torch.float32)
+    d.wt, d.dx = wt.data_ptr() if wt is not None else None, dx.data_ptr()
+    check(lib().usot_conv2d_dgrad_f32(stream(), C.byref(d)), 'usot_conv2d_dgrad_f32')
+    return dx
 
 
 def groupdw_desc(xs, zs, out, wsm, *, S, x_rep, OH, OW, Cc, x_cs, x_co, z_cs, z_co, cols=0):

@@ -6,8 +6,8 @@ reference lib/models/models.py:298-306, modules.py:61-135, connect.py:12-74,
 104-121, 160-219, 284-292) and record each convolution's geometry so that
 `usot_amd.engine` can lower the graph to HIP launches.  Calling `forward` on a
 holder raises: there is deliberately no torch fallback for the tensor math.
-The one exception is `GroupDWSlots.forward`, which hands its tensors to the differentiable HIP
-binding of `usot_amd.autograd` (device tensors only).
+The exceptions are `GroupDWSlots.forward` and `ConvSlot.forward`, which hand their tensors to the differentiable HIP
+bindings of `usot_amd.autograd` (device tensors only).
 """
 import torch
 import torch.nn as nn
@@ -34,8 +34,11 @@ class ConvSlot(nn.Module):
         ow = (w + 2 * self.pad[1] - self.dil[1] * (self.kw - 1) - 1) // self.stride + 1
         return oh, ow
 
-    def forward(self, *a, **k):
-        raise RuntimeError('ConvSlot is a parameter holder; the HIP engine does the math')
+    def forward(self, x):
+        """The bare convolution (no BatchNorm, no activation) of an NCHW device tensor; differentiable
+        (usot_amd.autograd.conv2d).  The engine does not come through here: it lowers the folded graph to HIP launches."""
+        from . import autograd
+        return autograd.conv2d(x, self.weight, self.bias, self.stride, self.pad, self.dil)
 
 
 class NormSlot(nn.Module):
