@@ -133,6 +133,7 @@ int usot_conv_tile_info(int tile, int *bm, int *bn);           /* tile ids are 1
 int usot_conv_tile_built(int tile);                            /* 1: compiled into this library (the routed tiles; every id with -DUSOT_EXPERIMENTS) */
 int usot_experiments_built(void);                              /* 1: the library was built with -DUSOT_EXPERIMENTS */
 int usot_conv_tile_name(int tile, char *buf, int len);         /* kernel symbol of the tile */
+int usot_conv_tile_launch(int tile, int *threads, int *lds_bytes);   /* workgroup size and dynamic LDS of the tile; zeros: not built */
 int usot_conv_tile_dyn(int tile);                              /* 1: the tile honours usot_conv_desc.n_dyn (run-time image count) */
 int usot_conv_tile_xsplit(int tile);                           /* 1: the tile reads a split input map (usot_conv_desc.x_split) */
 int usot_conv_tile_wfrag(int tile);                            /* 1: the tile streams its filters in fragment order; 2: split-fp16 bank + w_scale */

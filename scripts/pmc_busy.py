@@ -11,30 +11,9 @@ constants'.)  Prints the per-kernel table (what profiles/roundN_*_mfma_busy.txt 
 `peak_sustained`.  Kernel keys: conv_igemm_f32 tiles as hip.tile_name() prints them, everything else the demangled symbol
 up to its argument list.
     python scripts/pmc_busy.py RESULTS.db [out.json [commit [min_us]]]"""
-import json, os, re, sqlite3, sys
+import json, os, sqlite3, sys
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from pmc_lp_traffic import short
-
-
-def f32_tile_name(sym):
-    """The key bench.py uses for an fp32 conv tile (usot_conv_tile_name), from the kernel symbol; None for other kernels."""
-    m = re.search(r'conv_igemm_f32(_v[23])?<([\d, ]+)>', sym)
-    if not m:
-        return None
-    fam, a = m.group(1) or '', [int(v) for v in m.group(2).split(',')]
-    if fam == '':
-        return 'conv_igemm_f32<%d,%d>' % (a[0], a[1])
-    if fam == '_v3':
-        d = a[5] if len(a) > 5 else 1
-        if len(a) > 7 and a[7] in (4, 5):             # split-fp16 tiles (usot_conv_tile_name: ...,NPW=n,PF=4|5)
-            return 'conv_igemm_f32_v3<%d,%d,BK=%d,D=%d,NPW=%d,PF=%d>' % (a[0], a[1], a[4], d, a[6], a[7])
-        if len(a) > 6 and a[6] == 8:
-            return 'conv_igemm_f32_v3<%d,%d,BK=%d,D=%d,NPW=8>' % (a[0], a[1], a[4], d)
-        return ('conv_igemm_f32_v3<%d,%d,BK=%d,D=%d>' % (a[0], a[1], a[4], d)) if d > 1 else ('conv_igemm_f32_v3<%d,%d,BK=%d>' % (a[0], a[1], a[4]))
-    ksw = a[5] if len(a) > 5 else 1
-    if ksw > 1:
-        return 'conv_igemm_f32_v2<%d,%d,%d,%d> ksw=%d' % (a[0], a[1], a[4], ksw, ksw)
-    return 'conv_igemm_f32_v2<%d,%d,BK=%d>' % (a[0], a[1], a[4])
+from pmc_lp_traffic import f32_tile_name, short
 
 
 def main(argv):

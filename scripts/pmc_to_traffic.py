@@ -4,7 +4,8 @@ TCC block has 4 counter slots) into HBM bytes per launch per conv kernel, with t
 correction of MI355X_MICROARCH.md §HBM: FETCH_SIZE counts 128-byte requests at 64 bytes for
 wide (16 B/lane) coalesced reads -> doubled.  Writes profiles/pmc_traffic.json, which bench.py
 reads for `roofline.traffic`."""
-import json, re, sqlite3, sys
+import json, sqlite3, sys
+from pmc_lp_traffic import f32_tile_name
 
 def _csrc_tree():
     import os, sys
@@ -29,31 +30,10 @@ def per_kernel(path):
     return {k: (n, t / n) for k, (n, t) in agg.items()}
 
 
-def norm(sym):
-    m = re.search(r'conv_igemm_f32(_v[23])?<([\d, ]+)>', sym)
-    if not m:
-        return None
-    fam, a = m.group(1) or '', [int(v) for v in m.group(2).split(',')]
-    if fam == '':
-        return 'conv_igemm_f32<%d,%d>' % (a[0], a[1])
-    if fam == '_v3':
-        d = a[5] if len(a) > 5 else 1                 # register prefetch depth (tile ids 37-52)
-        if len(a) > 7 and a[7] in (4, 5):             # split-fp16 tiles (usot_conv_tile_name: ...,NPW=n,PF=4|5)
-            return 'conv_igemm_f32_v3<%d,%d,BK=%d,D=%d,NPW=%d,PF=%d>' % (a[0], a[1], a[4], d, a[6], a[7])
-        if len(a) > 6 and a[6] == 8:                  # eight producer waves (tile ids 53-60)
-            return 'conv_igemm_f32_v3<%d,%d,BK=%d,D=%d,NPW=8>' % (a[0], a[1], a[4], d)
-        return ('conv_igemm_f32_v3<%d,%d,BK=%d,D=%d>' % (a[0], a[1], a[4], d)) if d > 1 else \
-               ('conv_igemm_f32_v3<%d,%d,BK=%d>' % (a[0], a[1], a[4]))
-    ksw = a[5] if len(a) > 5 else 1
-    if ksw > 1:
-        return 'conv_igemm_f32_v2<%d,%d,%d,%d> ksw=%d' % (a[0], a[1], a[4], ksw, ksw)
-    return 'conv_igemm_f32_v2<%d,%d,BK=%d>' % (a[0], a[1], a[4])
-
-
 fetch, write = per_kernel(sys.argv[1]), per_kernel(sys.argv[2])
 out = {}
 for sym, (n, kb) in fetch.items():
-    k = norm(sym)
+    k = f32_tile_name(sym)
     if k is None:
         continue
     wkb = write.get(sym, (0, 0.0))[1]
