@@ -448,6 +448,50 @@ int     usot_conv2d_wgrad_geometry(int *bco, int *bk, int *chunk);              
 int     usot_conv_pack_dgrad_f32(void *stream, const float *w, float *wt, int Cout, int Cin, int KH, int KW);
 int     usot_conv2d_dgrad_route(const usot_conv_grad_desc *d);                   /* host only: 1 = route A, 2 = route B */
 
+/* ---- BatchNorm2d on NHWC fp32 maps, forward and gradients (csrc/batchnorm.hip; every nn.BatchNorm2d of connect.py, with the
+ * ReLU that follows most of them).  A map is [M][C], M = N*H*W rows of C channels, C % 4 == 0 (every access is 16 bytes).
+ *   training: mean[c] = sum_m x[m][c] / M,  var[c] = sum_m (x[m][c] - mean[c])^2 / M  (biased),  invstd = 1 / sqrt(var + eps)
+ *   eval:     mean = running_mean,          invstd = 1 / sqrt(running_var + eps)
+ *   xhat = (x - mean) * invstd,   pre = fma(xhat, gamma, beta),   y = act ? max(pre, 0) : pre
+ *   dy' = act ? dy * (pre > 0) : dy;   dbeta[c] = sum_m dy'[m][c];   dgamma[c] = sum_m dy'[m][c] * xhat[m][c]
+ *   dx = gamma * invstd * (dy' - dbeta / M - xhat * dgamma / M)  in training,   gamma * invstd * dy'  in eval
+ * The backward pass recomputes `pre` from x with the forward's own instructions (it never reads y), so its mask is the sign of
+ * the forward's output bit for bit; it therefore needs x, gamma, beta (with act) and the statistics the forward used.
+ * Reductions run over `slices` ranges of row steps (a step is *rows rows, usot_batchnorm_geometry; slice s owns the steps
+ * [steps*s/slices, steps*(s+1)/slices), steps = ceil(M / *rows), so a slice may own no row at all) times blocks of *chans
+ * channels; each workgroup leaves its partial - (mean, M2) of its rows, or the two sums - in ws[slice][2][C] with plain stores,
+ * and the second launch (normalise / dx) combines the slices of its channels in slice order (Chan's formula on (count, mean,
+ * M2), counts from the geometry; slices without rows are never read).  No atomics; every sum has an order fixed by
+ * (M, C, slices): equal inputs give equal bits.  Launches: forward training 2, forward eval 1, backward 2 - or 1 for an eval
+ * call that wants dx only (no reduction), and the second is a single row of workgroups when dx is not wanted.
+ * A launch writes its outputs and ws[0 .. usot_batchnorm_ws_floats) and nothing else; x, dy, gamma, beta are only read.
+ * USOT_EINVAL, before the device is touched and with every output unwritten: d NULL, M < 1 (M < 2 in training: the unbiased
+ * variance divides by M - 1), C < 4 or C % 4 != 0, training / act outside {0, 1}, slices < 0 or > M, eps negative or not
+ * finite, a NULL pointer the call needs, a misaligned pointer (16 bytes). */
+typedef struct usot_bn_desc {
+    const float *x;                 /* [M][C] input map; both entry points */
+    const float *gamma, *beta;      /* [C] affine; forward: both; backward: gamma, and beta when act = 1 (the mask) */
+    float *running_mean;            /* [C]; training forward: updated in place when non-NULL, r = (1 - momentum) r + momentum mean; */
+    float *running_var;             /*      the variance with the unbiased estimate var * M / (M - 1).  eval: read only, required */
+    float *y;                       /* [M][C] forward output; the backward pass does not read it */
+    float *save_mean, *save_invstd; /* [C]; training: written by the forward, read by the backward; unused in eval */
+    const float *dy;                /* [M][C] gradient of y; backward only */
+    float *dx;                      /* [M][C]; NULL = not wanted */
+    float *dgamma, *dbeta;          /* [C]; NULL = not wanted */
+    float *ws;                      /* usot_batchnorm_ws_floats(d) floats; contents before the call do not matter; may be NULL for the
+                                     * launches without a reduction (eval forward, eval backward of dx alone) */
+    int32_t M, C;                   /* rows (N*H*W) and channels */
+    float eps, momentum;
+    int32_t training;               /* 0 = running statistics, 1 = batch statistics */
+    int32_t act;                    /* USOT_ACT_NONE | USOT_ACT_RELU */
+    int32_t slices;                 /* row slices of the reductions; 0 = the launcher's choice (usot_batchnorm_slices) */
+} usot_bn_desc;
+int     usot_batchnorm_fwd_f32(void *stream, const usot_bn_desc *d);             /* y; training: save_*, running_* */
+int     usot_batchnorm_bwd_f32(void *stream, const usot_bn_desc *d);             /* dx, dgamma, dbeta: the ones that are non-NULL */
+int64_t usot_batchnorm_ws_floats(const usot_bn_desc *d);                         /* host only: 2 * slices * C (either entry point) */
+int     usot_batchnorm_slices(const usot_bn_desc *d);                            /* host only: the split a slices = 0 launch takes */
+int     usot_batchnorm_geometry(int *rows, int *chans);                          /* host only: rows per step, channels per workgroup */
+
 /* ---- fused GroupDW on NHWC (connect.py:86-102): three depthwise xcorrs and the
  * softmax(weight)-weighted sum in one pass, no intermediate maps.
  *   branch b: x_b NHWC [XS][OH+hk_b-1][OW+wk_b-1] (pixel stride x_cs, channel offset x_co)

@@ -1,9 +1,9 @@
-"""torch.autograd bindings of the native depthwise cross-correlation (reference lib/models/connect.py:86-102,147-157) and of
-the fp32 convolution (every nn.Conv2d of connect.py).
+"""torch.autograd bindings of the native depthwise cross-correlation (reference lib/models/connect.py:86-102,147-157), of
+the fp32 convolution (every nn.Conv2d of connect.py) and of BatchNorm2d with its ReLU (every nn.BatchNorm2d of connect.py).
 
-Forward values are `usot_amd.hip.xcorr_depthwise`'s and `usot_amd.hip.conv2d`'s, bit for bit; the gradients come from the
-kernels of csrc/xcorr_grad.hip and csrc/conv_grad.hip.  First-order gradients only, fp32 only, device tensors only (no CPU
-implementation: CPU tensors raise `hip.HipError`).
+Forward values are `usot_amd.hip.xcorr_depthwise`'s, `usot_amd.hip.conv2d`'s and `usot_amd.hip.batch_norm_forward`'s, bit for
+bit; the gradients come from the kernels of csrc/xcorr_grad.hip, csrc/conv_grad.hip and csrc/batchnorm.hip.  First-order
+gradients only, fp32 only, device tensors only (no CPU implementation: CPU tensors raise `hip.HipError`).
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -162,3 +162,49 @@ def conv2d(x, weight, bias=None, stride=1, padding=0, dilation=1, relu=False):
     if _wants_grad(x, weight, bias):
         return Conv2dFunction.apply(x, weight, bias, int(stride), pad, dil, bool(relu))
     return _conv2d_forward(x, weight, bias, int(stride), pad, dil, bool(relu))[2].permute(0, 3, 1, 2)
+
+
+class BatchNormFunction(torch.autograd.Function):
+    """y = [relu](batch_norm(x)) on an NCHW-shaped tensor; the kernels work on the NHWC map, which is what backward keeps
+    (with the statistics the forward normalised with: the ReLU mask is recomputed from them, y is not saved)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, training, momentum, eps, relu):
+        xh = hip.to_nhwc(x.detach())
+        w, b = weight.detach(), bias.detach()
+        y, mean, invstd = hip.batch_norm_forward(xh, w, b, running_mean, running_var, training=training, momentum=momentum,
+                                                 eps=eps, relu=relu)
+        ctx.cfg = (training, eps, relu)
+        if training:
+            ctx.save_for_backward(xh, w, b, mean, invstd)
+        else:
+            ctx.save_for_backward(xh, w, b, running_mean, running_var)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        xh, w, b, s0, s1 = ctx.saved_tensors
+        training, eps, relu = ctx.cfg
+        saved = (s0, s1, None, None) if training else (None, None, s0, s1)
+        dx, dw, db = hip.batch_norm_backward(hip.to_nhwc(dout), xh, w, b, *saved, training=training, eps=eps, relu=relu,
+                                             need=ctx.needs_input_grad[:3])
+        return (None if dx is None else dx.permute(0, 3, 1, 2)), dw, db, None, None, None, None, None, None
+
+
+def batch_norm(x, weight, bias, running_mean, running_var, training, momentum=0.1, eps=1e-5, relu=False):
+    """Differentiable `F.batch_norm` (affine, C % 4 == 0) on an NCHW device tensor, optionally with the ReLU behind it fused.
+    The result is NCHW-shaped over channels-last memory; a channels-last input (what `conv2d` returns) is not copied.
+    training: batch statistics, and running_mean / running_var (None = not tracked) move on the device whether or not a
+    gradient is recorded.  Eval: the running statistics normalise."""
+    hip._dev(x), hip._dev(weight), hip._dev(bias)
+    if x.dim() != 4 or weight.dim() != 1 or x.shape[1] != weight.shape[0]:
+        raise hip.HipError('batch_norm: input %s and weight %s do not fit' % (tuple(x.shape), tuple(weight.shape)))
+    if not training and (running_mean is None or running_var is None):
+        raise hip.HipError('batch_norm: eval mode needs the running statistics')
+    args = (running_mean, running_var, bool(training), float(momentum), float(eps), bool(relu))
+    if _wants_grad(x, weight, bias):
+        return BatchNormFunction.apply(x, weight, bias, *args)
+    y = hip.batch_norm_forward(hip.to_nhwc(x), weight.detach(), bias.detach(), running_mean, running_var, training=args[2],
+                               momentum=args[3], eps=args[4], relu=args[5])[0]
+    return y.permute(0, 3, 1, 2)

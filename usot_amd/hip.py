@@ -37,6 +37,7 @@ EXPORTS = (
     'usot_plan_add_groupdw_multi_dyn', 'usot_conf_fusion_reduce_map_f32', 'usot_plan_add_conf_reduce_map', 'usot_conv_tile_dyn',
     'usot_conv2d_wgrad_f32', 'usot_conv2d_dgrad_f32', 'usot_conv2d_wgrad_ws_floats', 'usot_conv2d_wgrad_psplit', 'usot_conv2d_wgrad_geometry',
     'usot_conv_pack_dgrad_f32', 'usot_conv2d_dgrad_route',
+    'usot_batchnorm_fwd_f32', 'usot_batchnorm_bwd_f32', 'usot_batchnorm_ws_floats', 'usot_batchnorm_slices', 'usot_batchnorm_geometry',
 )
 
 
@@ -71,6 +72,15 @@ class GradDesc(C.Structure):
                 ('KH', C.c_int32), ('KW', C.c_int32), ('stride', C.c_int32),
                 ('pad_h', C.c_int32), ('pad_w', C.c_int32), ('dil_h', C.c_int32), ('dil_w', C.c_int32),
                 ('psplit', C.c_int32), ('route', C.c_int32)]
+
+
+class BnDesc(C.Structure):
+    """usot_bn_desc"""
+    _fields_ = [('x', C.c_void_p), ('gamma', C.c_void_p), ('beta', C.c_void_p), ('running_mean', C.c_void_p),
+                ('running_var', C.c_void_p), ('y', C.c_void_p), ('save_mean', C.c_void_p), ('save_invstd', C.c_void_p),
+                ('dy', C.c_void_p), ('dx', C.c_void_p), ('dgamma', C.c_void_p), ('dbeta', C.c_void_p), ('ws', C.c_void_p),
+                ('M', C.c_int32), ('C', C.c_int32), ('eps', C.c_float), ('momentum', C.c_float),
+                ('training', C.c_int32), ('act', C.c_int32), ('slices', C.c_int32)]
 
 
 class GroupDWDesc(C.Structure):
@@ -251,6 +261,12 @@ def lib():
         L.usot_conv2d_wgrad_ws_floats.restype = C.c_int64
         L.usot_conv2d_wgrad_geometry.argtypes = [C.POINTER(C.c_int)] * 3
         L.usot_conv_pack_dgrad_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4
+        for name in ('usot_batchnorm_fwd_f32', 'usot_batchnorm_bwd_f32'):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+        for name in ('usot_batchnorm_ws_floats', 'usot_batchnorm_slices'):
+            getattr(L, name).argtypes = [C.c_void_p]
+        L.usot_batchnorm_ws_floats.restype = C.c_int64
+        L.usot_batchnorm_geometry.argtypes = [C.POINTER(C.c_int)] * 2
         L.usot_conf_fusion_reduce_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4
         L.usot_prroi_pool_forward_f32.argtypes = ([C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_float]
                                                   + [C.c_int64] * 8)
@@ -685,6 +701,102 @@ def conv2d_backward_x(dy, w, x_shape, *, KH, KW, stride=1, pad=(0, 0), dil=(1, 1
     d.wt, d.dx = wt.data_ptr() if wt is not None else None, dx.data_ptr()
     check(lib().usot_conv2d_dgrad_f32(stream(), C.byref(d)), 'usot_conv2d_dgrad_f32')
     return dx
+
+
+def bn_desc(*, M, C, eps=1e-5, momentum=0.1, training=True, act=ACT_NONE, slices=0, x=None, gamma=None, beta=None,
+            running_mean=None, running_var=None, y=None, save_mean=None, save_invstd=None, dy=None, dx=None, dgamma=None,
+            dbeta=None, ws=None):
+    """usot_bn_desc of an [M][C] map; pointers are addresses (or None)"""
+    d = BnDesc()
+    d.x, d.gamma, d.beta, d.running_mean, d.running_var, d.y, d.save_mean, d.save_invstd, d.dy, d.dx, d.dgamma, d.dbeta, d.ws = (
+        v or None for v in (x, gamma, beta, running_mean, running_var, y, save_mean, save_invstd, dy, dx, dgamma, dbeta, ws))
+    d.M, d.C, d.eps, d.momentum, d.training, d.act, d.slices = M, C, eps, momentum, int(training), act, slices
+    return d
+
+
+def batchnorm_geometry():
+    """(rows staged per step, channels per workgroup) of the batch-norm kernels"""
+    v = [C.c_int(0) for _ in range(2)]
+    check(lib().usot_batchnorm_geometry(*[C.byref(i) for i in v]), 'usot_batchnorm_geometry')
+    return tuple(i.value for i in v)
+
+
+def _bn_map(what, t, channels=None):
+    """a dense [..., C] device map -> (M, C)"""
+    _dev(t)
+    if t.dim() < 2 or not t.is_contiguous() or (channels is not None and t.shape[-1] != channels):
+        raise HipError('%s: a dense NHWC map%s expected, got shape %s strides %s'
+                       % (what, '' if channels is None else ' of %d channels' % channels, tuple(t.shape), t.stride()))
+    return t.numel() // t.shape[-1], t.shape[-1]
+
+
+def _bn_vec(what, name, t, channels):
+    _dev(t)
+    if t.dim() != 1 or t.shape[0] != channels or not t.is_contiguous():
+        raise HipError('%s: %s of shape %s does not hold %d channels' % (what, name, tuple(t.shape), channels))
+    return t.data_ptr()
+
+
+def _bn_ws(d, device):
+    need = lib().usot_batchnorm_ws_floats(C.byref(d))
+    if need < 0:
+        check(int(need), 'usot_batchnorm_ws_floats')
+    return torch.empty((need,), device=device, dtype=torch.float32)
+
+
+def batch_norm_forward(x_nhwc, gamma, beta, running_mean, running_var, *, training, momentum=0.1, eps=1e-5, relu=False,
+                       slices=0):
+    """BatchNorm2d (and the ReLU behind it) of a dense NHWC map [..., C], C % 4 == 0 -> (y, save_mean, save_invstd).
+    training: batch statistics; running_mean / running_var (each may be None) are updated in place on the device, and
+    save_mean / save_invstd are what `batch_norm_backward` needs.  Eval: the running statistics normalise, and the two saved
+    vectors are None."""
+    what = 'batch_norm_forward'
+    M, Cc = _bn_map(what, x_nhwc)
+    d = bn_desc(M=M, C=Cc, eps=eps, momentum=momentum, training=training, act=ACT_RELU if relu else ACT_NONE, slices=slices,
+                x=x_nhwc.data_ptr(), gamma=_bn_vec(what, 'gamma', gamma, Cc), beta=_bn_vec(what, 'beta', beta, Cc))
+    if running_mean is not None or not training:
+        d.running_mean = _bn_vec(what, 'running_mean', running_mean, Cc)
+    if running_var is not None or not training:
+        d.running_var = _bn_vec(what, 'running_var', running_var, Cc)
+    y = torch.empty(x_nhwc.shape, device=x_nhwc.device, dtype=torch.float32)
+    d.y = y.data_ptr()
+    mean = invstd = ws = None
+    if training:
+        mean = torch.empty((Cc,), device=x_nhwc.device, dtype=torch.float32)
+        invstd = torch.empty((Cc,), device=x_nhwc.device, dtype=torch.float32)
+        ws = _bn_ws(d, x_nhwc.device)
+        d.save_mean, d.save_invstd, d.ws = mean.data_ptr(), invstd.data_ptr(), ws.data_ptr()
+    check(lib().usot_batchnorm_fwd_f32(stream(), C.byref(d)), 'usot_batchnorm_fwd_f32')
+    return y, mean, invstd
+
+
+def batch_norm_backward(dy, x_nhwc, gamma, beta, save_mean, save_invstd, running_mean, running_var, *, training, eps=1e-5,
+                        relu=False, need=(True, True, True), slices=0):
+    """Gradients of `batch_norm_forward` -> (dx | None, dgamma | None, dbeta | None), the ones `need` asks for.  dy and
+    x_nhwc are dense NHWC maps of one shape.  training: save_mean / save_invstd of the forward call; eval: the running
+    statistics it read.  beta is read with relu only: the mask is recomputed from x, not read from y."""
+    what = 'batch_norm_backward'
+    M, Cc = _bn_map(what, x_nhwc)
+    _bn_map(what, dy, Cc)
+    if dy.shape != x_nhwc.shape:
+        raise HipError('%s: grad_output %s does not belong to input %s' % (what, tuple(dy.shape), tuple(x_nhwc.shape)))
+    d = bn_desc(M=M, C=Cc, eps=eps, training=training, act=ACT_RELU if relu else ACT_NONE, slices=slices,
+                x=x_nhwc.data_ptr(), dy=dy.data_ptr(), gamma=_bn_vec(what, 'gamma', gamma, Cc))
+    if relu:
+        d.beta = _bn_vec(what, 'beta', beta, Cc)
+    if training:
+        d.save_mean, d.save_invstd = _bn_vec(what, 'save_mean', save_mean, Cc), _bn_vec(what, 'save_invstd', save_invstd, Cc)
+    else:
+        d.running_mean = _bn_vec(what, 'running_mean', running_mean, Cc)
+        d.running_var = _bn_vec(what, 'running_var', running_var, Cc)
+    need_x, need_g, need_b = (bool(v) for v in need)
+    dx = torch.empty(x_nhwc.shape, device=dy.device, dtype=torch.float32) if need_x else None
+    dg = torch.empty((Cc,), device=dy.device, dtype=torch.float32) if need_g else None
+    db = torch.empty((Cc,), device=dy.device, dtype=torch.float32) if need_b else None
+    ws = _bn_ws(d, dy.device) if need_g or need_b or (training and need_x) else None
+    d.dx, d.dgamma, d.dbeta, d.ws = ptr(dx), ptr(dg), ptr(db), ptr(ws)
+    check(lib().usot_batchnorm_bwd_f32(stream(), C.byref(d)), 'usot_batchnorm_bwd_f32')
+    return dx, dg, db
 
 
 def groupdw_desc(xs, zs, out, wsm, *, S, x_rep, OH, OW, Cc, x_cs, x_co, z_cs, z_co, cols=0):

@@ -6,8 +6,9 @@ reference lib/models/models.py:298-306, modules.py:61-135, connect.py:12-74,
 104-121, 160-219, 284-292) and record each convolution's geometry so that
 `usot_amd.engine` can lower the graph to HIP launches.  Calling `forward` on a
 holder raises: there is deliberately no torch fallback for the tensor math.
-The exceptions are `GroupDWSlots.forward` and `ConvSlot.forward`, which hand their tensors to the differentiable HIP
-bindings of `usot_amd.autograd` (device tensors only).
+The exceptions are `GroupDWSlots.forward`, `ConvSlot.forward` and `NormSlot.forward` (with `conv_norm`, which chains the
+latter two over one conv - BN [- ReLU] holder), which hand their tensors to the differentiable HIP bindings of
+`usot_amd.autograd` (device tensors only).
 """
 import torch
 import torch.nn as nn
@@ -42,9 +43,11 @@ class ConvSlot(nn.Module):
 
 
 class NormSlot(nn.Module):
-    """BatchNorm2d affine + running statistics (eval-mode only on this path)."""
+    """BatchNorm2d affine + running statistics.  The engine folds them into the conv banks; `forward` is the differentiable
+    operator, in the module's own mode."""
 
     eps = 1e-5
+    momentum = 0.1
 
     def __init__(self, c):
         super().__init__()
@@ -54,8 +57,16 @@ class NormSlot(nn.Module):
         self.register_buffer('running_var', torch.ones(c))
         self.register_buffer('num_batches_tracked', torch.tensor(0, dtype=torch.long))
 
-    def forward(self, *a, **k):
-        raise RuntimeError('NormSlot is a parameter holder; the HIP engine does the math')
+    def forward(self, x, relu=False):
+        """nn.BatchNorm2d (and, with `relu`, the ReLU behind it) of an NCHW device tensor; differentiable
+        (usot_amd.autograd.batch_norm).  self.training chooses batch or running statistics; a training-mode call moves the
+        running statistics and counts itself in num_batches_tracked, all on the device."""
+        from . import autograd
+        y = autograd.batch_norm(x, self.weight, self.bias, self.running_mean, self.running_var, self.training, self.momentum,
+                                self.eps, relu)
+        if self.training:
+            self.num_batches_tracked.add_(1)
+        return y
 
 
 class _Gap(nn.Module):
@@ -67,6 +78,15 @@ class _Gap(nn.Module):
 
 def _seq(*mods):
     return nn.Sequential(*mods)
+
+
+def conv_norm(seq, x):
+    """Run a `_seq(ConvSlot, NormSlot[, _Gap])` holder as the reference runs its nn.Sequential: conv -> BN, with the ReLU
+    fused into the BN kernel iff the `_Gap` is there.  Differentiable; NCHW device tensors."""
+    if len(seq) not in (2, 3) or not isinstance(seq[0], ConvSlot) or not isinstance(seq[1], NormSlot) \
+            or (len(seq) == 3 and not isinstance(seq[2], _Gap)):
+        raise TypeError('conv_norm: a (ConvSlot, NormSlot[, _Gap]) sequence expected')
+    return seq[1](seq[0](x), relu=len(seq) == 3)
 
 
 class BottleneckSlots(nn.Module):
