@@ -778,8 +778,46 @@ int usot_plan_run(void *plan, void *stream);
 /* per-op mean milliseconds per launch (HIP events on `stream`, eager, program order, each op
  * launched `reps` times between its two events), blocking */
 int usot_plan_profile(void *plan, void *stream, int frames, int reps, float *ms_per_op);
-/* info[4] = {kind, conv tile id, ksplit, groups} of op i (kind: 0 conv, 1 stem, 2 maxpool,
- * 3 groupdw, 4 conf_reduce, 5 prroi, 6 permute, 7 decode, 8 fork, 9 join)                */
+/* info[4] = {kind, conv tile id, ksplit, groups} of op i.  tile: kind 0 - the tile the launcher would pick NOW
+ * (usot_conv_resolve_tile on the first descriptor), kind 11 - the descriptor's tile field, else 0; ksplit / groups: kind 0 (first
+ * descriptor), else 1.  The kinds - an op's kind names its ADDER, the entry point it launches is listed behind it.  The numbers
+ * are FROZEN: bench.py, the tests and the scripts match on them; a new kind takes the next free number.
+ *    0  conv, conv_batch          usot_conv2d_f32 (one problem) | usot_conv2d_batch_f32
+ *    1  stem, stem_mu             usot_stem_conv_mu_f32
+ *    2  maxpool                   usot_maxpool3x3s2_f32
+ *    3  groupdw, groupdw_multi, groupdw_multi_dyn   usot_groupdw_multi_dyn_f32;  groupdw_multi_lp   usot_groupdw_multi_lp
+ *    4  conf_reduce, conf_reduce_map   usot_conf_fusion_reduce_map_f32;  conf_reduce_lp   usot_conf_fusion_reduce_lp
+ *    5  prroi                     usot_prroi_pool_forward_f32
+ *    6  permute                   usot_permute4_f32
+ *    7  decode                    usot_decode_dev_f32
+ *    8  fork                      (no launch: the lane waits for lane 0)
+ *    9  join                      (no launch: lane 0 waits for the lane)
+ *   10  rows_copy                 usot_rows_copy_f32
+ *   11  conv_lp, conv_bf16        usot_conv2d_lp
+ *   12  cvt_lp, cvt_bf16          usot_cvt_f32_to_lp
+ *   13  maxpool_lp, maxpool_bf16  usot_maxpool3x3s2_lp
+ *   14  stem_pool_lp              usot_stem_pool_lp
+ *   15  rows_copy_multi           usot_rows_copy_multi_f32
+ *   16  thin_conv                 usot_thin_conv3x3_f32
+ *   17  stem_pool, stem_pool_ind, stem_pool_mu   usot_stem_pool_mu_f32
+ *   18  pw_pair                   usot_pw_pair_lp (dtype 0 | 1) | usot_pw_pair_f32 (2) | usot_pw_pair_f32s (3)
+ *   19  pw_single                 usot_pw_single_f32
+ *   20  stream_conv3x3            usot_stream_conv3x3_f32
+ *   21  pw_triple                 usot_pw_triple_f32
+ *   22  pw_panel                  usot_pw_panel_lp
+ *   23  pw_panel_pair             usot_pw_panel_pair_lp
+ *   24  conv3x3_halo              usot_conv3x3_halo_lp
+ *   25  pw_kstream                usot_pw_kstream_lp
+ *   26  conv_kstream              usot_conv_kstream_lp
+ *   27  bneck_first               usot_bneck_first_lp
+ *   28  bneck_tail                usot_bneck_tail_lp
+ *   29  conv_pw                   usot_conv_pw_lp
+ *   30  conv_pw_pair              usot_conv_pw_pair_lp
+ *   31  conv_pw_ov                usot_conv_pw_ov_lp
+ *   32  rows_append_gather        usot_rows_append_gather_f32;  rows_append_gather_dedupe   usot_rows_append_gather_dedupe_f32
+ *   33  decode_batch              usot_decode_batch_f32
+ *   34  rows_append_gather_batch  usot_rows_append_gather_batch_f32
+ *   35  crop_resize_batch         usot_crop_resize_batch_u8_f32 */
 int usot_plan_op_info(void *plan, int i, int *info);
 int usot_conv_resolve_tile(const usot_conv_desc *d);
 

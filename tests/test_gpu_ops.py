@@ -1019,6 +1019,97 @@ def test_plan_run_capture_and_lanes():
         L.usot_plan_destroy(plan)
 
 
+def test_plan_owns_its_by_pointer_arguments():
+    """A plan keeps its OWN copy of everything an adder receives by pointer - the descriptors of a batched conv, the src / dst /
+    row_len arrays of rows_copy_multi, the fresh / bank / picked / row_len arrays of rows_append_gather.  After the adds the
+    caller's ctypes arrays are overwritten in place with a valid DECOY problem (other live buffers of the same sizes, NaN-filled
+    outputs; row lengths of 4, so that any mix of real and decoy arguments stays inside every buffer): a plan that read the
+    caller's memory at replay would write the decoy, not fault.  The eager run, the captured run and usot_plan_profile must
+    each leave the real outputs bit-equal to the immediate entry points' and the decoy outputs all-NaN.
+    The convolutions are 1x1, N = 1, H = W = 5, Cout = 16 with Cin = 32: the fp32 conv launcher takes Cin % 32 == 0 only
+    (include/usot_hip.h), 32 is its smallest."""
+    import ctypes as C
+    L = hip.lib()
+    g = torch.Generator().manual_seed(29)
+    rnd = lambda *shape: torch.randn(*shape, generator=g).to(DEV)
+    nan = lambda *shape: g_full(shape, float('nan'))
+    vp = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+    all_nan = lambda ts: all(bool(torch.isnan(t).all()) for t in ts)
+
+    def conv_descs(xs, ws, ys):
+        return [hip.conv_desc(x.data_ptr(), w.data_ptr(), None, y.data_ptr(), N=1, H=5, W=5, Cin=32, OH=5, OW=5, Cout=16, KH=1, KW=1)
+                for x, w, y in zip(xs, ws, ys)]
+
+    # the real problem, its immediate results, and the decoy
+    cx, cw = [rnd(1, 5, 5, 32) for _ in range(4)], [rnd(16, 32) / 6 for _ in range(4)]
+    cy, cy_ref, cy_decoy = ([nan(1, 5, 5, 16) for _ in range(4)] for _ in range(3))
+    dx, dw = [rnd(1, 5, 5, 32) for _ in range(4)], [rnd(16, 32) / 6 for _ in range(4)]
+    lens = [4, 8, 12, 16]
+    idx = torch.tensor([4, 0, 5], dtype=torch.int32, device=DEV)
+    gsrc, gsrc_decoy = ([rnd(6, n) for n in lens] for _ in range(2))
+    gdst, gdst_ref, gdst_decoy = ([nan(3, n) for n in lens] for _ in range(3))
+    alens = [16, 8, 12, 4]
+    aidx = torch.tensor([1, 2, 5, 2], dtype=torch.int32, device=DEV)        # picks rows 1, 2, 5; appends to row aidx[3] = 2
+    fresh, fresh_decoy = ([rnd(1, n) for n in alens] for _ in range(2))
+    bank0 = [rnd(6, n) for n in alens]
+    bank, bank_ref = [b.clone() for b in bank0], [b.clone() for b in bank0]
+    bank_decoy = [nan(6, n) for n in alens]
+    picked, picked_ref, picked_decoy = ([nan(3, n) for n in alens[1:]] for _ in range(3))
+
+    ref = (hip.ConvDesc * 4)(*conv_descs(cx, cw, cy_ref))
+    hip.check(L.usot_conv2d_batch_f32(hip.stream(), ref, 4), 'conv batch')
+    hip.check(L.usot_rows_copy_multi_f32(hip.stream(), 4, vp(gsrc), hip.ptr(idx), vp(gdst_ref), 3, (C.c_int32 * 4)(*lens), 0, None), 'gather')
+    hip.check(L.usot_rows_append_gather_f32(hip.stream(), vp(fresh), vp(bank_ref), vp(picked_ref), (C.c_int32 * 4)(*alens),
+                                            hip.ptr(aidx), 3, 3), 'append gather')
+    torch.cuda.synchronize()
+    assert not any(bool(torch.isnan(t).any()) for t in cy_ref + gdst_ref + bank_ref + picked_ref)
+
+    plan = C.c_void_p(L.usot_plan_create())
+    descs = (hip.ConvDesc * 4)(*conv_descs(cx, cw, cy))
+    src, dst, rl = vp(gsrc), vp(gdst), (C.c_int32 * 4)(*lens)
+    fr, bk, pk, arl = vp(fresh), vp(bank), vp(picked), (C.c_int32 * 4)(*alens)
+    hip.check(L.usot_plan_add_conv_batch(plan, descs, 4))
+    hip.check(L.usot_plan_add_rows_copy_multi(plan, 4, src, hip.ptr(idx), dst, 3, rl, 0, None))
+    hip.check(L.usot_plan_add_rows_append_gather(plan, fr, bk, pk, arl, hip.ptr(aidx), 3, 3))
+    assert L.usot_plan_size(plan) == 3
+    # the caller's arrays now describe the decoy
+    for i, d in enumerate(conv_descs(dx, dw, cy_decoy)):
+        descs[i] = d
+    for arr, ts in ((src, gsrc_decoy), (dst, gdst_decoy), (fr, fresh_decoy), (bk, bank_decoy), (pk, picked_decoy)):
+        for i, t in enumerate(ts):
+            arr[i] = t.data_ptr()
+    for i in range(4):
+        rl[i] = arl[i] = 4
+
+    def reset():
+        for t in cy + gdst + picked:
+            t.fill_(float('nan'))
+        for b, b0 in zip(bank, bank0):
+            b.copy_(b0)
+
+    def check(what):
+        torch.cuda.synchronize()
+        for got, want in zip(cy + gdst + bank + picked, cy_ref + gdst_ref + bank_ref + picked_ref):
+            assert torch.equal(got, want), what
+        assert all_nan(cy_decoy + gdst_decoy + bank_decoy + picked_decoy), what
+
+    hip.check(L.usot_plan_run(plan, hip.stream()))
+    check('eager')
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        reset()
+        s.synchronize()
+        hip.check(L.usot_plan_capture(plan, hip.stream()))
+        hip.check(L.usot_plan_run(plan, hip.stream()))
+        s.synchronize()
+    check('captured')
+    reset()
+    ms = (C.c_float * 3)()
+    hip.check(L.usot_plan_profile(plan, hip.stream(), 1, 2, ms))
+    check('profile')
+    L.usot_plan_destroy(plan)
+
+
 def test_decode_dev_writes_roi_and_tag(gold_host):
     import ctypes as C
     p = orc.Hyper(255)

@@ -107,6 +107,59 @@ class BneckDesc(C.Structure):
                 ('y', C.c_void_p), ('t', C.c_void_p), ('N', C.c_int32), ('H', C.c_int32), ('W', C.c_int32)]
 
 
+# (immediate entry point, its plan adder, argtypes): the two take the same arguments after the first void * (the stream | the plan),
+# so lib() sets each signature once for both names
+PAIRS = (
+    ('usot_conv2d_f32', 'usot_plan_add_conv', [C.c_void_p, C.c_void_p]),
+    ('usot_conv2d_batch_f32', 'usot_plan_add_conv_batch', [C.c_void_p, C.c_void_p, C.c_int]),
+    ('usot_thin_conv3x3_f32', 'usot_plan_add_thin_conv', [C.c_void_p, C.c_void_p, C.c_int]),
+    ('usot_conv2d_bf16', 'usot_plan_add_conv_bf16', [C.c_void_p, C.c_void_p]),
+    ('usot_conv2d_lp', 'usot_plan_add_conv_lp', [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    ('usot_cvt_f32_to_bf16', 'usot_plan_add_cvt_bf16', [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    ('usot_maxpool3x3s2_bf16', 'usot_plan_add_maxpool_bf16', [C.c_void_p] * 3 + [C.c_int] * 6),
+    ('usot_stem_pool_lp', 'usot_plan_add_stem_pool_lp', [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_float] * 3),
+    ('usot_pw_pair_lp', 'usot_plan_add_pw_pair', [C.c_void_p, C.c_void_p, C.c_int]),
+    ('usot_pw_panel_lp', 'usot_plan_add_pw_panel', [C.c_void_p] * 6 + [C.c_int] * 5),
+    ('usot_pw_panel_pair_lp', 'usot_plan_add_pw_panel_pair', [C.c_void_p, C.POINTER(PwPairDesc), C.c_int]),
+    ('usot_conv_pw_lp', 'usot_plan_add_conv_pw', [C.c_void_p] * 6 + [C.c_int]),
+    ('usot_conv_pw_pair_lp', 'usot_plan_add_conv_pw_pair', [C.c_void_p, C.c_void_p, C.POINTER(PwPairDesc), C.c_int]),
+    ('usot_conv_pw_ov_lp', 'usot_plan_add_conv_pw_ov', [C.c_void_p, C.c_void_p, C.POINTER(PwPairDesc), C.c_int, C.c_void_p]),
+    ('usot_conv3x3_halo_lp', 'usot_plan_add_conv3x3_halo', [C.c_void_p] * 5 + [C.c_int] * 7),
+    ('usot_bneck_first_lp', 'usot_plan_add_bneck_first', [C.c_void_p, C.c_void_p, C.c_int]),
+    ('usot_bneck_tail_lp', 'usot_plan_add_bneck_tail', [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    ('usot_pw_kstream_lp', 'usot_plan_add_pw_kstream', [C.c_void_p] * 5 + [C.c_long] + [C.c_int] * 4),
+    ('usot_conv_kstream_lp', 'usot_plan_add_conv_kstream', [C.c_void_p] * 5 + [C.c_int] * 10),
+    ('usot_pw_single_f32', 'usot_plan_add_pw_single', [C.c_void_p] * 6 + [C.c_int] * 4),
+    ('usot_pw_triple_f32', 'usot_plan_add_pw_triple', [C.c_void_p] * 5 + [C.c_int] * 10),
+    ('usot_stream_conv3x3_f32', 'usot_plan_add_stream_conv3x3', [C.c_void_p] * 6 + [C.c_int] * 12),
+    ('usot_stem_conv_f32', 'usot_plan_add_stem', [C.c_void_p] * 5 + [C.c_int] * 5),
+    ('usot_stem_conv_mu_f32', 'usot_plan_add_stem_mu', [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_float] * 3),
+    ('usot_stem_pool_f32', 'usot_plan_add_stem_pool', [C.c_void_p] * 5 + [C.c_int] * 7),
+    ('usot_stem_pool_ind_f32', 'usot_plan_add_stem_pool_ind', [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p]),
+    ('usot_stem_pool_mu_f32', 'usot_plan_add_stem_pool_mu', [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p] + [C.c_float] * 3),
+    ('usot_maxpool3x3s2_f32', 'usot_plan_add_maxpool', [C.c_void_p] * 3 + [C.c_int] * 6),
+    ('usot_groupdw_f32', 'usot_plan_add_groupdw', [C.c_void_p, C.c_void_p]),
+    ('usot_groupdw_multi_f32', 'usot_plan_add_groupdw_multi', [C.c_void_p, C.c_void_p, C.c_int]),
+    ('usot_groupdw_multi_lp', 'usot_plan_add_groupdw_multi_lp', [C.c_void_p, C.c_void_p, C.c_int, C.c_int]),
+    ('usot_groupdw_multi_dyn_f32', 'usot_plan_add_groupdw_multi_dyn', [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    ('usot_conf_fusion_reduce_f32', 'usot_plan_add_conf_reduce', [C.c_void_p] * 3 + [C.c_int] * 4),
+    ('usot_conf_fusion_reduce_lp', 'usot_plan_add_conf_reduce_lp', [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 5),
+    ('usot_conf_fusion_reduce_map_f32', 'usot_plan_add_conf_reduce_map', [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
+    ('usot_prroi_pool_forward_f32', 'usot_plan_add_prroi', [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_float] + [C.c_int64] * 8),
+    ('usot_permute4_f32', 'usot_plan_add_permute', [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_int64] * 4),
+    ('usot_decode_dev_f32', 'usot_plan_add_decode',
+     [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_float] + [C.c_double] * 2 + [C.c_void_p] * 2),
+    ('usot_decode_batch_f32', 'usot_plan_add_decode_batch',
+     [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float] + [C.c_double] * 2 + [C.c_void_p] * 2),
+    ('usot_rows_copy_f32', 'usot_plan_add_rows_copy', [C.c_void_p] * 4 + [C.c_int] * 3),
+    ('usot_rows_copy_multi_f32', 'usot_plan_add_rows_copy_multi',
+     [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    ('usot_rows_append_gather_f32', 'usot_plan_add_rows_append_gather', [C.c_void_p] * 6 + [C.c_int, C.c_int]),
+    ('usot_rows_append_gather_dedupe_f32', 'usot_plan_add_rows_append_gather_dedupe', [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]),
+    ('usot_rows_append_gather_batch_f32', 'usot_plan_add_rows_append_gather_batch', [C.c_void_p] * 6 + [C.c_int] * 3),
+    ('usot_crop_resize_batch_u8_f32', 'usot_plan_add_crop_resize_batch', [C.c_void_p] * 3 + [C.c_int] * 2),
+)
+
 _lib = None
 
 
@@ -124,87 +177,27 @@ def lib():
         L.usot_conv_ws_floats.restype = C.c_int64
         L.usot_plan_create.restype = C.c_void_p
         L.usot_plan_destroy.argtypes = [C.c_void_p]
-        for name in ('usot_plan_add_conv', 'usot_plan_add_groupdw'):
-            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
-        L.usot_plan_add_stem.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] * 5
-        L.usot_plan_add_maxpool.argtypes = [C.c_void_p] + [C.c_void_p] * 2 + [C.c_int] * 6
-        L.usot_plan_add_conf_reduce.argtypes = [C.c_void_p] + [C.c_void_p] * 2 + [C.c_int] * 4
-        L.usot_plan_add_prroi.argtypes = ([C.c_void_p] + [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float]
-                                          + [C.c_int64] * 8)
-        L.usot_plan_add_permute.argtypes = [C.c_void_p] + [C.c_void_p] * 2 + [C.c_int] * 4 + [C.c_int64] * 4
-        L.usot_plan_add_decode.argtypes = ([C.c_void_p] + [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_float]
-                                           + [C.c_double] * 2 + [C.c_void_p] * 2)
-        L.usot_plan_add_rows_copy.argtypes = [C.c_void_p] + [C.c_void_p] * 3 + [C.c_int] * 3
-        L.usot_rows_copy_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 3
-        L.usot_thin_conv3x3_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.usot_stem_pool_f32.argtypes = [C.c_void_p] * 5 + [C.c_int] * 7
-        L.usot_plan_add_stem_pool.argtypes = [C.c_void_p] * 5 + [C.c_int] * 7
-        L.usot_plan_add_stem_pool_ind.argtypes = [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p]
-        L.usot_stem_pool_ind_f32.argtypes = [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p]
-        L.usot_conv3x3_halo_lp.argtypes = [C.c_void_p] * 5 + [C.c_int] * 7
-        L.usot_plan_add_conv3x3_halo.argtypes = [C.c_void_p] * 5 + [C.c_int] * 7
+        for immediate, plan_add, sig in PAIRS:
+            getattr(L, immediate).argtypes = getattr(L, plan_add).argtypes = sig
         L.usot_conv3x3_halo_supported.argtypes = [C.c_int] * 2
-        L.usot_bneck_first_lp.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.usot_plan_add_bneck_first.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.usot_bneck_first_supported.argtypes = [C.c_int] * 4
-        L.usot_bneck_tail_lp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-        L.usot_plan_add_bneck_tail.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.usot_bneck_tail_supported.argtypes = [C.c_int] * 3
         L.usot_bw_probe.argtypes = [C.c_void_p] * 3 + [C.c_int64, C.c_int]
-        L.usot_conv_kstream_lp.argtypes = [C.c_void_p] * 5 + [C.c_int] * 10
-        L.usot_plan_add_conv_kstream.argtypes = [C.c_void_p] * 5 + [C.c_int] * 10
         L.usot_conv_kstream_supported.argtypes = [C.c_int] * 4
-        L.usot_pw_kstream_lp.argtypes = [C.c_void_p] * 5 + [C.c_long] + [C.c_int] * 4
-        L.usot_plan_add_pw_kstream.argtypes = [C.c_void_p] * 5 + [C.c_long] + [C.c_int] * 4
         L.usot_pw_kstream_supported.argtypes = [C.c_int] * 2
-        L.usot_pw_panel_lp.argtypes = [C.c_void_p] * 6 + [C.c_int] * 5
-        L.usot_plan_add_pw_panel.argtypes = [C.c_void_p] * 6 + [C.c_int] * 5
         L.usot_pw_panel_supported.argtypes = [C.c_int] * 2
         L.usot_pw_panel_pair_supported.argtypes = [C.c_int] * 3
         L.usot_pw_panel_pixels.argtypes = [C.c_int] * 3
         L.usot_pw_panel_min_pixels.argtypes = [C.c_int] * 2
-        L.usot_pw_panel_pair_lp.argtypes = [C.c_void_p, C.POINTER(PwPairDesc), C.c_int]
-        L.usot_plan_add_pw_panel_pair.argtypes = [C.c_void_p, C.POINTER(PwPairDesc), C.c_int]
-        L.usot_conv_pw_lp.argtypes = [C.c_void_p] * 6 + [C.c_int]
-        L.usot_plan_add_conv_pw.argtypes = [C.c_void_p] * 6 + [C.c_int]
         L.usot_conv_pw_supported.argtypes = [C.c_int] * 3
         L.usot_conv_pw_pixels.argtypes = [C.c_int64]
-        L.usot_conv_pw_pair_lp.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PwPairDesc), C.c_int]
-        L.usot_plan_add_conv_pw_pair.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PwPairDesc), C.c_int]
         L.usot_conv_pw_pair_supported.argtypes = [C.c_int] * 3
-        L.usot_conv_pw_ov_lp.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PwPairDesc), C.c_int, C.c_void_p]
-        L.usot_plan_add_conv_pw_ov.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(PwPairDesc), C.c_int, C.c_void_p]
         L.usot_conv_pw_ov_supported.argtypes = [C.c_int] * 3
         L.usot_conv_pw_ov_ws_bytes.argtypes = [C.c_int64]
         L.usot_conv_pw_ov_ws_bytes.restype = C.c_int64
         L.usot_conv_pw_ov_trace.argtypes = [C.c_void_p]
-        L.usot_stem_pool_mu_f32.argtypes = [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p] + [C.c_float] * 3
-        L.usot_plan_add_stem_pool_mu.argtypes = [C.c_void_p] * 5 + [C.c_int] * 7 + [C.c_void_p] + [C.c_float] * 3
-        L.usot_plan_add_stem_mu.argtypes = [C.c_void_p] + [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float] * 3
-        L.usot_stem_conv_mu_f32.argtypes = [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_float] * 3
-        L.usot_plan_add_thin_conv.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.usot_rows_copy_multi_f32.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        L.usot_plan_add_rows_copy_multi.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        L.usot_rows_append_gather_f32.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int]
-        L.usot_plan_add_rows_append_gather.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int]
         L.usot_crop_resize_u8_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 9
-        L.usot_decode_batch_f32.argtypes = [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float] + [C.c_double] * 2 + [C.c_void_p] * 2
-        L.usot_plan_add_decode_batch.argtypes = [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_float] + [C.c_double] * 2 + [C.c_void_p] * 2
-        L.usot_rows_append_gather_dedupe_f32.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
-        L.usot_plan_add_rows_append_gather_dedupe.argtypes = [C.c_void_p] * 6 + [C.c_int, C.c_int, C.c_void_p]
-        L.usot_groupdw_multi_dyn_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.usot_plan_add_groupdw_multi_dyn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.usot_conf_fusion_reduce_map_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]
-        L.usot_plan_add_conf_reduce_map.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]
         L.usot_conv_tile_dyn.argtypes = [C.c_int]
-        L.usot_rows_append_gather_batch_f32.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3
-        L.usot_plan_add_rows_append_gather_batch.argtypes = [C.c_void_p] * 6 + [C.c_int] * 3
-        L.usot_crop_resize_batch_u8_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 2
-        L.usot_plan_add_crop_resize_batch.argtypes = [C.c_void_p] * 3 + [C.c_int] * 2
-        L.usot_plan_add_conv_bf16.argtypes = [C.c_void_p, C.c_void_p]
-        L.usot_plan_add_conv_lp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-        L.usot_pw_pair_lp.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.usot_plan_add_pw_pair.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.usot_pw_pair_layout.argtypes = [C.c_int] * 4 + [C.POINTER(C.c_int32)] * 2
         L.usot_pw_pair_supported.argtypes = [C.c_int] * 3
         L.usot_pw_pair_f32.argtypes = [C.c_void_p, C.c_void_p]
@@ -213,25 +206,11 @@ def lib():
         L.usot_pw_pair_f32s_supported.argtypes = [C.c_int] * 3
         L.usot_pw_pair_f32_ws_floats.argtypes = [C.c_int] * 4
         L.usot_pw_pair_f32_ws_floats.restype = C.c_int64
-        L.usot_pw_single_f32.argtypes = [C.c_void_p] * 6 + [C.c_int] * 4
         L.usot_pw_single_f32_supported.argtypes = [C.c_int] * 2
-        L.usot_plan_add_pw_single.argtypes = [C.c_void_p] * 6 + [C.c_int] * 4
-        L.usot_stream_conv3x3_f32.argtypes = [C.c_void_p] * 6 + [C.c_int] * 12
-        L.usot_plan_add_stream_conv3x3.argtypes = [C.c_void_p] * 6 + [C.c_int] * 12
         L.usot_stream_conv3x3_f32_supported.argtypes = [C.c_int] * 2
-        L.usot_pw_triple_f32.argtypes = [C.c_void_p] * 5 + [C.c_int] * 10
-        L.usot_plan_add_pw_triple.argtypes = [C.c_void_p] * 5 + [C.c_int] * 10
         L.usot_pw_triple_f32_supported.argtypes = [C.c_int] * 4
         L.usot_plan_add_cvt_lp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
         L.usot_plan_add_maxpool_lp.argtypes = [C.c_void_p] + [C.c_void_p] * 2 + [C.c_int] * 7
-        L.usot_conv2d_lp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-        L.usot_stem_pool_lp.argtypes = [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_float] * 3
-        L.usot_plan_add_stem_pool_lp.argtypes = [C.c_void_p] * 5 + [C.c_int] * 8 + [C.c_float] * 3
-        L.usot_plan_add_cvt_bf16.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-        L.usot_plan_add_maxpool_bf16.argtypes = [C.c_void_p] + [C.c_void_p] * 2 + [C.c_int] * 6
-        L.usot_conv2d_bf16.argtypes = [C.c_void_p, C.c_void_p]
-        L.usot_cvt_f32_to_bf16.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-        L.usot_maxpool3x3s2_bf16.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6
         L.usot_plan_fork.argtypes = [C.c_void_p, C.c_int]
         L.usot_plan_join.argtypes = [C.c_void_p, C.c_int]
         L.usot_plan_run.argtypes = [C.c_void_p, C.c_void_p]
@@ -239,18 +218,6 @@ def lib():
         L.usot_plan_size.argtypes = [C.c_void_p]
         L.usot_plan_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.usot_plan_op_info.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-        L.usot_conv2d_f32.argtypes = [C.c_void_p, C.c_void_p]
-        L.usot_conv2d_batch_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.usot_plan_add_conv_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.usot_groupdw_f32.argtypes = [C.c_void_p, C.c_void_p]
-        L.usot_groupdw_multi_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.usot_plan_add_groupdw_multi.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.usot_plan_add_groupdw_multi_lp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-        L.usot_groupdw_multi_lp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-        L.usot_conf_fusion_reduce_lp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 5
-        L.usot_plan_add_conf_reduce_lp.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 5
-        L.usot_stem_conv_f32.argtypes = [C.c_void_p] * 5 + [C.c_int] * 5
-        L.usot_maxpool3x3s2_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 6
         L.usot_xcorr_depthwise_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5
         L.usot_xcorr_depthwise_bwd_x_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float]
         L.usot_xcorr_depthwise_bwd_k_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float]
@@ -267,9 +234,6 @@ def lib():
             getattr(L, name).argtypes = [C.c_void_p]
         L.usot_batchnorm_ws_floats.restype = C.c_int64
         L.usot_batchnorm_geometry.argtypes = [C.POINTER(C.c_int)] * 2
-        L.usot_conf_fusion_reduce_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4
-        L.usot_prroi_pool_forward_f32.argtypes = ([C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_float]
-                                                  + [C.c_int64] * 8)
         L.PrRoIPoolingForwardGpu.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float, C.c_int]
         L.PrRoIPoolingForwardGpu.restype = None
         L.usot_prroi_pool_backward_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_float]
@@ -277,11 +241,8 @@ def lib():
         for name in ('PrRoIPoolingBackwardGpu', 'PrRoIPoolingCoorBackwardGpu'):
             getattr(L, name).argtypes = [C.c_void_p] * 6 + [C.c_int] * 5 + [C.c_float, C.c_int, C.c_int]
             getattr(L, name).restype = None
-        L.usot_permute4_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_int64] * 4
         L.usot_decode_f32.argtypes = ([C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_float]
                                       + [C.c_double] * 4)
-        L.usot_decode_dev_f32.argtypes = ([C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_float] + [C.c_double] * 2
-                                          + [C.c_void_p] * 2)
         L.usot_conv_tile_info.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.usot_conv_bf16_tile_info.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.usot_conv_pack_wfrag_f32.argtypes = [C.c_void_p] * 3 + [C.c_int] * 2
