@@ -492,6 +492,57 @@ int64_t usot_batchnorm_ws_floats(const usot_bn_desc *d);                        
 int     usot_batchnorm_slices(const usot_bn_desc *d);                            /* host only: the split a slices = 0 launch takes */
 int     usot_batchnorm_geometry(int *rows, int *chans);                          /* host only: rows per step, channels per workgroup */
 
+/* ---- Conf_Fusion on separate confidence and value maps, forward and gradients (csrc/head_grad.hip; connect.py:123-144 behind
+ * unfolded, training-mode BatchNorms - the inference engine's usot_conf_fusion_reduce_* work on the interleaved [conf | value]
+ * layout of folded convs and have no gradient).  conf and value are NHWC maps [B*M][P][C] (P = H*W pixels, C % 4 == 0: every
+ * access is 16 bytes), map b*M + m being memory slot m of batch element b; out and dout are [B][P][C].
+ *   e_m = exp(min(max(conf_m, -6), 4)),   S = sum_m e_m  (m = 0 .. M-1, in that order),   w_m = e_m / S
+ *   out = sum_m w_m * value_m             (in m order: the reference's association - normalise, then weight, then add)
+ *   dvalue_m = w_m * dout,                dconf_m = [-6 <= conf_m <= 4] * w_m * (value_m - out) * dout
+ * The clamp mask is inclusive (torch.clamp's gradient).  The backward pass recomputes e, S and out from conf and value: nothing
+ * but the two inputs is saved.  e_m and S are the forward's, bit for bit; `out` is re-formed in float64 from the same e_m,
+ * because value_m - out cancels when one weight dominates (M = 1: exactly 0).  One launch per call, one f32x4 lane per (b, p, c/4).
+ * Algorithmic traffic: forward (2M + 1) * B*P*C*4 bytes, backward (4M + 1) * B*P*C*4 bytes (value is not read when dconf is not
+ * wanted).  A launch writes its outputs and nothing else; conf, value and dout are only read.
+ * USOT_EINVAL, before the device is touched and with every output unwritten: d NULL, B, M or P < 1, C < 4 or C % 4 != 0, a NULL
+ * pointer the call needs (forward: conf, value, out; backward: conf, dout, and value with dconf), a misaligned pointer (16 bytes).
+ * A backward call that wants neither gradient is USOT_OK without a launch. */
+typedef struct usot_conf_fusion_desc {
+    const float *conf, *value;      /* [B*M][P][C] inputs; both entry points */
+    float *out;                     /* [B][P][C] forward output; the backward pass does not read it */
+    const float *dout;              /* [B][P][C] gradient of out; backward only */
+    float *dconf, *dvalue;          /* [B*M][P][C]; NULL = not wanted */
+    int32_t B, M, P, C;             /* batch, memory slots per batch element, pixels per map, channels */
+} usot_conf_fusion_desc;
+int     usot_conf_fusion_fwd_f32(void *stream, const usot_conf_fusion_desc *d);  /* out */
+int     usot_conf_fusion_bwd_f32(void *stream, const usot_conf_fusion_desc *d);  /* dconf, dvalue: the ones that are non-NULL */
+
+/* ---- the box epilogue y = exp(adjust * p + bias[c]) with its gradients (csrc/head_grad.hip; connect.py:236-237 with `adjust`
+ * and `bias` as learnable parameters - the inference engine fuses it into a folded conv as USOT_ACT_EXP).  p, y, dy and dp are
+ * [R][4] (R = N*H*W rows of the bbox_pred conv's NHWC output); adjust (1 float) and bias (4 floats) are read from DEVICE memory.
+ *   y[r][c] = exp(fma(adjust, p[r][c], bias[c]))
+ *   g = dy * y  (y recomputed from p),   dp = adjust * g,   dbias[c] = sum_r g[r][c],   dadjust = sum_{r,c} g[r][c] * p[r][c]
+ * Each workgroup of the backward launch sums its rows in a fixed tree and leaves five partials in ws[workgroup][5] with plain
+ * stores; a second launch of one workgroup merges the partials in float64 in an order fixed by R.  No atomics: equal inputs give
+ * equal bits.  Launches: forward 1; backward 2, or 1 when only dp is wanted (no reduction, ws may be NULL).
+ * A launch writes its outputs and ws[0 .. usot_box_exp_ws_floats) and nothing else; p, dy, adjust and bias are only read.
+ * USOT_EINVAL, before the device is touched and with every output unwritten: d NULL, R < 1, C != 4, a NULL pointer the call needs
+ * (forward: p, adjust, bias, y; backward: p, adjust, bias, dy, and ws with dadjust or dbias), a misaligned pointer (16 bytes).  A
+ * backward call that wants nothing is USOT_OK without a launch. */
+typedef struct usot_box_exp_desc {
+    const float *p;                 /* [R][4] input; both entry points */
+    const float *adjust, *bias;     /* 1 and 4 floats in device memory; both entry points */
+    float *y;                       /* [R][4] forward output; the backward pass does not read it */
+    const float *dy;                /* [R][4] gradient of y; backward only */
+    float *dp;                      /* [R][4]; NULL = not wanted */
+    float *dadjust, *dbias;         /* 1 and 4 floats; NULL = not wanted */
+    float *ws;                      /* usot_box_exp_ws_floats(d) floats; contents before the call do not matter */
+    int32_t R, C;                   /* rows, and channels: 4 */
+} usot_box_exp_desc;
+int     usot_box_exp_fwd_f32(void *stream, const usot_box_exp_desc *d);          /* y */
+int     usot_box_exp_bwd_f32(void *stream, const usot_box_exp_desc *d);          /* dp, dadjust, dbias: the ones that are non-NULL */
+int64_t usot_box_exp_ws_floats(const usot_box_exp_desc *d);                      /* host only: 5 * ceil(R / 256) */
+
 /* ---- fused GroupDW on NHWC (connect.py:86-102): three depthwise xcorrs and the
  * softmax(weight)-weighted sum in one pass, no intermediate maps.
  *   branch b: x_b NHWC [XS][OH+hk_b-1][OW+wk_b-1] (pixel stride x_cs, channel offset x_co)

@@ -1,9 +1,12 @@
 """torch.autograd bindings of the native depthwise cross-correlation (reference lib/models/connect.py:86-102,147-157), of
-the fp32 convolution (every nn.Conv2d of connect.py) and of BatchNorm2d with its ReLU (every nn.BatchNorm2d of connect.py).
+the fp32 convolution (every nn.Conv2d of connect.py), of BatchNorm2d with its ReLU (every nn.BatchNorm2d of connect.py), of
+Conf_Fusion's clamp - exp - normalise - weighted sum (connect.py:129-142) and of the box epilogue exp(adjust * p + bias)
+(connect.py:236-237).
 
-Forward values are `usot_amd.hip.xcorr_depthwise`'s, `usot_amd.hip.conv2d`'s and `usot_amd.hip.batch_norm_forward`'s, bit for
-bit; the gradients come from the kernels of csrc/xcorr_grad.hip, csrc/conv_grad.hip and csrc/batchnorm.hip.  First-order
-gradients only, fp32 only, device tensors only (no CPU implementation: CPU tensors raise `hip.HipError`).
+Forward values are `usot_amd.hip.xcorr_depthwise`'s, `usot_amd.hip.conv2d`'s, `usot_amd.hip.batch_norm_forward`'s,
+`usot_amd.hip.conf_fusion_forward`'s and `usot_amd.hip.box_exp_forward`'s, bit for bit; the gradients come from the kernels of
+csrc/xcorr_grad.hip, csrc/conv_grad.hip, csrc/batchnorm.hip and csrc/head_grad.hip.  First-order gradients only, fp32 only,
+device tensors only (no CPU implementation: CPU tensors raise `hip.HipError`).
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -208,3 +211,67 @@ def batch_norm(x, weight, bias, running_mean, running_var, training, momentum=0.
     y = hip.batch_norm_forward(hip.to_nhwc(x), weight.detach(), bias.detach(), running_mean, running_var, training=args[2],
                                momentum=args[3], eps=args[4], relu=args[5])[0]
     return y.permute(0, 3, 1, 2)
+
+
+class ConfFusionFunction(torch.autograd.Function):
+    """out[b] = sum_m exp(clamp(conf[b*M + m], -6, 4)) / S[b] * value[b*M + m] on NCHW-shaped tensors; the kernels work on the
+    NHWC maps, which are all backward keeps: the weights and `out` are recomputed."""
+
+    @staticmethod
+    def forward(ctx, conf, value, batch, mem_size):
+        ch, vh = hip.to_nhwc(conf.detach()), hip.to_nhwc(value.detach())
+        ctx.bm = (batch, mem_size)
+        ctx.save_for_backward(ch, vh)
+        return hip.conf_fusion_forward(ch, vh, batch, mem_size).permute(0, 3, 1, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        ch, vh = ctx.saved_tensors
+        dc, dv = hip.conf_fusion_backward(hip.to_nhwc(dout), ch, vh, *ctx.bm, need=ctx.needs_input_grad[:2])
+        return (None if dc is None else dc.permute(0, 3, 1, 2)), (None if dv is None else dv.permute(0, 3, 1, 2)), None, None
+
+
+def conf_fusion(conf, value, batch, mem_size):
+    """Differentiable fusion of the reference's `Conf_Fusion.forward` behind its two conv - BN - ReLU branches: `conf` and
+    `value` are NCHW-shaped device tensors [batch * mem_size, C, H, W] (C % 4 == 0), the result is [batch, C, H, W] over
+    channels-last memory; a channels-last input (what `batch_norm` returns) is not copied."""
+    hip._dev(conf), hip._dev(value)
+    batch, mem_size = int(batch), int(mem_size)
+    if conf.dim() != 4 or conf.shape != value.shape or conf.shape[0] != batch * mem_size:
+        raise hip.HipError('conf_fusion: conf %s and value %s are not two [%d * %d, C, H, W] maps'
+                           % (tuple(conf.shape), tuple(value.shape), batch, mem_size))
+    if _wants_grad(conf, value):
+        return ConfFusionFunction.apply(conf, value, batch, mem_size)
+    return hip.conf_fusion_forward(hip.to_nhwc(conf.detach()), hip.to_nhwc(value.detach()), batch, mem_size).permute(0, 3, 1, 2)
+
+
+class BoxExpFunction(torch.autograd.Function):
+    """y = exp(adjust * p + bias[c]) on an NCHW-shaped [N, 4, H, W] tensor; adjust and bias stay on the device.  Backward keeps
+    the NHWC map of p and the two parameters; y is recomputed."""
+
+    @staticmethod
+    def forward(ctx, p, adjust, bias):
+        ph, a, b = hip.to_nhwc(p.detach()), adjust.detach(), bias.detach()
+        ctx.save_for_backward(ph, a, b)
+        return hip.box_exp_forward(ph, a, b).permute(0, 3, 1, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        ph, a, b = ctx.saved_tensors
+        dp, da, db = hip.box_exp_backward(hip.to_nhwc(dy), ph, a, b, need=ctx.needs_input_grad[:3])
+        return (None if dp is None else dp.permute(0, 3, 1, 2)), da, db
+
+
+def box_exp(p, adjust, bias):
+    """Differentiable `torch.exp(adjust * p + bias)` of the reference's box head: `p` an NCHW-shaped device tensor [N, 4, H, W]
+    (the `bbox_pred` output; a channels-last one is not copied), `adjust` one float, `bias` four ([1, 4, 1, 1]).  The result is
+    NCHW-shaped over channels-last memory."""
+    hip._dev(p), hip._dev(adjust), hip._dev(bias)
+    if p.dim() != 4 or p.shape[1] != 4 or adjust.numel() != 1 or bias.numel() != 4:
+        raise hip.HipError('box_exp: p %s, adjust %s and bias %s are not [N, 4, H, W], one float and four'
+                           % (tuple(p.shape), tuple(adjust.shape), tuple(bias.shape)))
+    if _wants_grad(p, adjust, bias):
+        return BoxExpFunction.apply(p, adjust, bias)
+    return hip.box_exp_forward(hip.to_nhwc(p.detach()), adjust.detach(), bias.detach()).permute(0, 3, 1, 2)

@@ -83,6 +83,19 @@ class BnDesc(C.Structure):
                 ('training', C.c_int32), ('act', C.c_int32), ('slices', C.c_int32)]
 
 
+class ConfFusionDesc(C.Structure):
+    """usot_conf_fusion_desc"""
+    _fields_ = [('conf', C.c_void_p), ('value', C.c_void_p), ('out', C.c_void_p), ('dout', C.c_void_p), ('dconf', C.c_void_p),
+                ('dvalue', C.c_void_p), ('B', C.c_int32), ('M', C.c_int32), ('P', C.c_int32), ('C', C.c_int32)]
+
+
+class BoxExpDesc(C.Structure):
+    """usot_box_exp_desc"""
+    _fields_ = [('p', C.c_void_p), ('adjust', C.c_void_p), ('bias', C.c_void_p), ('y', C.c_void_p), ('dy', C.c_void_p),
+                ('dp', C.c_void_p), ('dadjust', C.c_void_p), ('dbias', C.c_void_p), ('ws', C.c_void_p),
+                ('R', C.c_int32), ('C', C.c_int32)]
+
+
 class GroupDWDesc(C.Structure):
     _fields_ = [('x', C.c_void_p * 3), ('z', C.c_void_p * 3), ('out', C.c_void_p),
                 ('hk', C.c_int32 * 3), ('wk', C.c_int32 * 3),
@@ -234,6 +247,11 @@ def lib():
             getattr(L, name).argtypes = [C.c_void_p]
         L.usot_batchnorm_ws_floats.restype = C.c_int64
         L.usot_batchnorm_geometry.argtypes = [C.POINTER(C.c_int)] * 2
+        # the head's gradient operators (csrc/head_grad.hip): bound here, not listed in EXPORTS (no plan adders, ABI 6 unchanged)
+        for name in ('usot_conf_fusion_fwd_f32', 'usot_conf_fusion_bwd_f32', 'usot_box_exp_fwd_f32', 'usot_box_exp_bwd_f32'):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
+        L.usot_box_exp_ws_floats.argtypes = [C.c_void_p]
+        L.usot_box_exp_ws_floats.restype = C.c_int64
         L.PrRoIPoolingForwardGpu.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float, C.c_int]
         L.PrRoIPoolingForwardGpu.restype = None
         L.usot_prroi_pool_backward_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_float]
@@ -758,6 +776,120 @@ def batch_norm_backward(dy, x_nhwc, gamma, beta, save_mean, save_invstd, running
     d.dx, d.dgamma, d.dbeta, d.ws = ptr(dx), ptr(dg), ptr(db), ptr(ws)
     check(lib().usot_batchnorm_bwd_f32(stream(), C.byref(d)), 'usot_batchnorm_bwd_f32')
     return dx, dg, db
+
+
+def conf_fusion_desc(*, B, M, P, C, conf=None, value=None, out=None, dout=None, dconf=None, dvalue=None):
+    """usot_conf_fusion_desc of [B*M][P][C] maps; pointers are addresses (or None)"""
+    d = ConfFusionDesc()
+    d.conf, d.value, d.out, d.dout, d.dconf, d.dvalue = (v or None for v in (conf, value, out, dout, dconf, dvalue))
+    d.B, d.M, d.P, d.C = B, M, P, C
+    return d
+
+
+def _cf_maps(what, conf, value, B, M):
+    """the two dense [B*M, ..., C] device maps of a Conf_Fusion call -> (P, C)"""
+    _bn_map(what, conf)
+    if value is not None:
+        _bn_map(what, value)
+        if value.shape != conf.shape:
+            raise HipError('%s: conf %s and value %s differ in shape' % (what, tuple(conf.shape), tuple(value.shape)))
+    B, M = int(B), int(M)
+    Cc = conf.shape[-1]
+    if B < 1 or M < 1 or conf.dim() < 3 or conf.shape[0] != B * M or Cc < 4 or Cc % 4:
+        raise HipError('%s: maps of shape %s are not [B*M = %d*%d, ..., C] with C %% 4 == 0' % (what, tuple(conf.shape), B, M))
+    return conf.numel() // (B * M * Cc), Cc
+
+
+def conf_fusion_forward(conf, value, B, M):
+    """Conf_Fusion (connect.py:129-142) of the dense NHWC maps conf and value [B*M, H, W, C] (map b*M + m: slot m of batch
+    element b), C % 4 == 0 -> out [B, H, W, C] = sum_m softmax-like weights exp(clamp(conf_m, -6, 4)) / S times value_m."""
+    what = 'conf_fusion_forward'
+    P, Cc = _cf_maps(what, conf, value, B, M)
+    out = torch.empty((int(B),) + tuple(conf.shape[1:]), device=conf.device, dtype=torch.float32)
+    d = conf_fusion_desc(B=int(B), M=int(M), P=P, C=Cc, conf=conf.data_ptr(), value=value.data_ptr(), out=out.data_ptr())
+    check(lib().usot_conf_fusion_fwd_f32(stream(), C.byref(d)), 'usot_conf_fusion_fwd_f32')
+    return out
+
+
+def conf_fusion_backward(dout, conf, value, B, M, need=(True, True)):
+    """Gradients of `conf_fusion_forward` -> (dconf | None, dvalue | None), the ones `need` asks for; dout is dense [B, H, W, C].
+    The weights and `out` are recomputed from conf and value."""
+    what = 'conf_fusion_backward'
+    P, Cc = _cf_maps(what, conf, value, B, M)
+    _bn_map(what, dout, Cc)
+    if tuple(dout.shape) != (int(B),) + tuple(conf.shape[1:]):
+        raise HipError('%s: grad_output %s does not belong to maps %s' % (what, tuple(dout.shape), tuple(conf.shape)))
+    need_c, need_v = (bool(v) for v in need)
+    dconf = torch.empty(conf.shape, device=conf.device, dtype=torch.float32) if need_c else None
+    dvalue = torch.empty(conf.shape, device=conf.device, dtype=torch.float32) if need_v else None
+    d = conf_fusion_desc(B=int(B), M=int(M), P=P, C=Cc, conf=conf.data_ptr(), value=value.data_ptr(), dout=dout.data_ptr())
+    d.dconf, d.dvalue = ptr(dconf), ptr(dvalue)
+    check(lib().usot_conf_fusion_bwd_f32(stream(), C.byref(d)), 'usot_conf_fusion_bwd_f32')
+    return dconf, dvalue
+
+
+def box_exp_desc(*, R, C=4, p=None, adjust=None, bias=None, y=None, dy=None, dp=None, dadjust=None, dbias=None, ws=None):
+    """usot_box_exp_desc of an [R][4] map; pointers are addresses (or None)"""
+    d = BoxExpDesc()
+    d.p, d.adjust, d.bias, d.y, d.dy, d.dp, d.dadjust, d.dbias, d.ws = (
+        v or None for v in (p, adjust, bias, y, dy, dp, dadjust, dbias, ws))
+    d.R, d.C = R, C
+    return d
+
+
+def box_exp_ws_floats(R):
+    """floats of workspace a box_exp_backward over R rows needs (host only)"""
+    need = lib().usot_box_exp_ws_floats(C.byref(box_exp_desc(R=int(R))))
+    if need < 0:
+        check(int(need), 'usot_box_exp_ws_floats')
+    return int(need)
+
+
+def box_exp_row_step():
+    """rows one workgroup of the box-exp reduction sums into one partial, read off the workspace query"""
+    one, r = box_exp_ws_floats(1), 1
+    while box_exp_ws_floats(r + 1) == one:
+        r += 1
+    return r
+
+
+def _box_args(what, p, adjust, bias):
+    _bn_map(what, p, 4)
+    for name, t, n in (('adjust', adjust, 1), ('bias', bias, 4)):
+        _dev(t)
+        if t.numel() != n or not t.is_contiguous():
+            raise HipError('%s: %s of shape %s does not hold %d float%s' % (what, name, tuple(t.shape), n, 's' * (n > 1)))
+    return p.numel() // 4
+
+
+def box_exp_forward(p, adjust, bias):
+    """y = exp(adjust * p + bias[c]) of a dense NHWC map p [..., 4]; adjust (1 float) and bias (4 floats) are device tensors and
+    are read on the device (connect.py:236-237)."""
+    what = 'box_exp_forward'
+    R = _box_args(what, p, adjust, bias)
+    y = torch.empty(p.shape, device=p.device, dtype=torch.float32)
+    d = box_exp_desc(R=R, p=p.data_ptr(), adjust=adjust.data_ptr(), bias=bias.data_ptr(), y=y.data_ptr())
+    check(lib().usot_box_exp_fwd_f32(stream(), C.byref(d)), 'usot_box_exp_fwd_f32')
+    return y
+
+
+def box_exp_backward(dy, p, adjust, bias, need=(True, True, True)):
+    """Gradients of `box_exp_forward` -> (dp | None, dadjust | None, dbias | None), the ones `need` asks for, dadjust and dbias
+    in the shapes of adjust and bias.  y is recomputed from p; the two sums have an order fixed by the row count."""
+    what = 'box_exp_backward'
+    R = _box_args(what, p, adjust, bias)
+    _bn_map(what, dy, 4)
+    if dy.shape != p.shape:
+        raise HipError('%s: grad_output %s does not belong to input %s' % (what, tuple(dy.shape), tuple(p.shape)))
+    need_p, need_a, need_b = (bool(v) for v in need)
+    dp = torch.empty(p.shape, device=p.device, dtype=torch.float32) if need_p else None
+    da = torch.empty(adjust.shape, device=p.device, dtype=torch.float32) if need_a else None
+    db = torch.empty(bias.shape, device=p.device, dtype=torch.float32) if need_b else None
+    ws = torch.empty((box_exp_ws_floats(R),), device=p.device, dtype=torch.float32) if need_a or need_b else None
+    d = box_exp_desc(R=R, p=p.data_ptr(), adjust=adjust.data_ptr(), bias=bias.data_ptr(), dy=dy.data_ptr())
+    d.dp, d.dadjust, d.dbias, d.ws = ptr(dp), ptr(da), ptr(db), ptr(ws)
+    check(lib().usot_box_exp_bwd_f32(stream(), C.byref(d)), 'usot_box_exp_bwd_f32')
+    return dp, da, db
 
 
 def groupdw_desc(xs, zs, out, wsm, *, S, x_rep, OH, OW, Cc, x_cs, x_co, z_cs, z_co, cols=0):

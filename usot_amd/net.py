@@ -7,8 +7,10 @@ reference lib/models/models.py:298-306, modules.py:61-135, connect.py:12-74,
 `usot_amd.engine` can lower the graph to HIP launches.  Calling `forward` on a
 holder raises: there is deliberately no torch fallback for the tensor math.
 The exceptions are `GroupDWSlots.forward`, `ConvSlot.forward` and `NormSlot.forward` (with `conv_norm`, which chains the
-latter two over one conv - BN [- ReLU] holder), which hand their tensors to the differentiable HIP bindings of
-`usot_amd.autograd` (device tensors only).
+latter two over one conv - BN [- ReLU] holder), and the head's holders built from them - `EncoderSlots.forward`,
+`ConfFusionSlots.forward` and `HeadSlots.forward` (the reference's `matrix`, `Conf_Fusion` and `box_tower_reg`) - which hand
+their tensors to the differentiable HIP bindings of `usot_amd.autograd` (device tensors only).  The neck, the backbone and the
+whole model still raise.
 """
 import torch
 import torch.nn as nn
@@ -165,6 +167,17 @@ class EncoderSlots(nn.Module):
                 self.add_module('%s_%s' % (name, side),
                                 _seq(ConvSlot(cin, cout, 3, dil=dil), NormSlot(cout), _Gap()))
 
+    def forward(self, z=None, x=None):
+        """reference connect.py:55-74 on NCHW device tensors: the three encodings of the template `z` and of the search map
+        `x`, each side None when its input is; differentiable (conv_norm).  All three convs of a side read the side's input,
+        as the reference's do.  The engine does not come through here."""
+        zs = xs = None
+        if x is not None:
+            xs = [conv_norm(getattr(self, name + '_s'), x) for name, _ in self.GEOMS]
+        if z is not None:
+            zs = [conv_norm(getattr(self, name + '_k'), z) for name, _ in self.GEOMS]
+        return zs, xs
+
 
 class GroupDWSlots(nn.Module):
     """reference connect.py:82-84: three branch logits, softmax-ed at use."""
@@ -188,12 +201,27 @@ class ConfFusionSlots(nn.Module):
         self.conf_gen = _seq(ConvSlot(c, c, 3, pad=1, bias=True), NormSlot(c), _Gap())
         self.value_gen = _seq(ConvSlot(c, c, 3, pad=1, bias=True), NormSlot(c), _Gap())
 
+    def forward(self, x):
+        """reference connect.py:123-144: `x` [B, M, C, H, W] on the device -> [B, C, H, W]; the two conv - BN - ReLU branches
+        over the [B*M, C, H, W] view, then the fusion kernel (usot_amd.autograd.conf_fusion).  Differentiable."""
+        from . import autograd
+        batch, mem_size, channel, h, w = x.shape
+        x = x.reshape(-1, channel, h, w)
+        return autograd.conf_fusion(conv_norm(self.conf_gen, x), conv_norm(self.value_gen, x), batch, mem_size)
+
 
 def _tower(c, n):
     mods = []
     for _ in range(n):
         mods += [ConvSlot(c, c, 3, pad=1, bias=True), NormSlot(c), _Gap()]
     return _seq(*mods)
+
+
+def _run_tower(seq, x):
+    """a `_tower` holder as the reference runs it: conv - BN - ReLU per stage"""
+    for i in range(0, len(seq), 3):
+        x = conv_norm(seq[i:i + 3], x)
+    return x
 
 
 class HeadSlots(nn.Module):
@@ -214,3 +242,38 @@ class HeadSlots(nn.Module):
         self.cls_memory_pred = ConvSlot(c, 1, 3, pad=1, bias=True)
         self.adjust = nn.Parameter(0.1 * torch.ones(1), requires_grad=False)
         self.bias = nn.Parameter(torch.ones(1, 4, 1, 1), requires_grad=False)
+
+    def forward(self, search, kernel=None, memory_kernel=None, memory_confidence=None, cls_x_store=None):
+        """reference connect.py:221-281 on NCHW device tensors, differentiable, in the module's mode; the same three call
+        forms and five-tuple results (None when neither kernel is given).  Only `memory_confidence.shape` is read (a CPU
+        tensor is fine).  Nothing in the call waits for the device besides GroupDW's copy of its three branch weights."""
+        from . import autograd
+        if kernel is not None:
+            cls_z, cls_x = self.cls_encode(kernel, search)
+            reg_z, reg_x = self.reg_encode(kernel, search)
+            cls_dw = self.cls_dw(cls_z, cls_x)
+            reg_dw = self.reg_dw(reg_z, reg_x)
+            x_bbox = autograd.box_exp(self.bbox_pred(_run_tower(self.bbox_tower, reg_dw)), self.adjust, self.bias)
+            cls = 0.1 * self.cls_pred(_run_tower(self.cls_tower, cls_dw))
+            if memory_kernel is None:
+                return x_bbox, cls, cls_x, reg_x, None
+        if memory_kernel is not None:
+            if cls_x_store is None:
+                cls_mem_zs, cls_x_store = self.cls_encode(memory_kernel, x=search)
+            else:
+                cls_mem_zs, _ = self.cls_encode(memory_kernel, x=None)
+            batch, mem_size = memory_confidence.shape
+            store_repeat = []
+            for t in cls_x_store:
+                _, c, h, w = t.shape
+                store_repeat.append(t.view(batch, 1, c, h, w).repeat(1, mem_size, 1, 1, 1).view(-1, c, h, w))
+            cls_mem_dw = self.cls_dw(cls_mem_zs, store_repeat)
+            _, c, h, w = cls_mem_dw.shape
+            cls_mem = 0.1 * self.cls_memory_pred(_run_tower(self.cls_memory_tower,
+                                                            self.conf_fusion(cls_mem_dw.reshape(batch, mem_size, c, h, w))))
+            if kernel is not None:
+                # the reference's loop variable leaves `cls_x` bound to the last encoded map here; no caller reads the third
+                # result of the combined call, and the encoded list is what the offline form returns
+                return x_bbox, cls, cls_x, reg_x, cls_mem
+            return None, None, None, None, cls_mem
+        return None
