@@ -492,6 +492,28 @@ int64_t usot_batchnorm_ws_floats(const usot_bn_desc *d);                        
 int     usot_batchnorm_slices(const usot_bn_desc *d);                            /* host only: the split a slices = 0 launch takes */
 int     usot_batchnorm_geometry(int *rows, int *chans);                          /* host only: rows per step, channels per workgroup */
 
+/* ---- BatchNorm2d with a residual operand, forward and gradients (csrc/batchnorm.hip; the tail of a ResNet bottleneck,
+ * out = relu(bn3(conv3(.)) + residual), modules.py:48-56).  Maps, statistics, slices and workspace are usot_bn_desc's; res and
+ * dres are [M][C] like x.
+ *   pre as in usot_bn_desc;   s = pre + res  (one float32 add, not contracted);   y = act ? max(s, 0) : s
+ *   dy' = act ? dy * (s > 0) : dy;   dres = dy';   dgamma, dbeta and dx as in usot_bn_desc with this dy'
+ * The statistics do not see the residual.  The backward pass recomputes s from x, res and the statistics the forward used, with
+ * the forward's own instructions (it never reads y): its mask is the sign of the forward's output bit for bit.  res is read for
+ * the mask only (act = 1), but is required in every call.
+ * Workspace: usot_batchnorm_ws_floats(&d->bn).  Launches as for usot_bn_desc: forward training 2, eval 1; backward 2 - or 1 when
+ * no reduction is needed: eval mode wanting only dx and / or dres, or any mode wanting only dres.
+ * A launch writes its outputs and the workspace and nothing else.  No output may alias an input (y or dres on res, dx on x ...):
+ * a workgroup reads rows that another may already have written.  Outputs may not alias each other either.
+ * USOT_EINVAL, before the device is touched and with every output unwritten: every case of usot_bn_desc, res NULL, a misaligned
+ * res or dres (16 bytes), a backward call that wants nothing (dx, dgamma, dbeta and dres all NULL). */
+typedef struct usot_bn_add_desc {
+    usot_bn_desc bn;                /* everything as documented for usot_bn_desc */
+    const float *res;               /* [M][C] residual, required */
+    float *dres;                    /* [M][C] gradient of res; NULL = not wanted */
+} usot_bn_add_desc;
+int     usot_batchnorm_add_fwd_f32(void *stream, const usot_bn_add_desc *d);     /* y; training: save_*, running_* */
+int     usot_batchnorm_add_bwd_f32(void *stream, const usot_bn_add_desc *d);     /* dx, dgamma, dbeta, dres: the non-NULL ones */
+
 /* ---- Conf_Fusion on separate confidence and value maps, forward and gradients (csrc/head_grad.hip; connect.py:123-144 behind
  * unfolded, training-mode BatchNorms - the inference engine's usot_conf_fusion_reduce_* work on the interleaved [conf | value]
  * layout of folded convs and have no gradient).  conf and value are NHWC maps [B*M][P][C] (P = H*W pixels, C % 4 == 0: every

@@ -213,6 +213,56 @@ def batch_norm(x, weight, bias, running_mean, running_var, training, momentum=0.
     return y.permute(0, 3, 1, 2)
 
 
+class BatchNormAddFunction(torch.autograd.Function):
+    """y = [relu](batch_norm(x) + residual) on NCHW-shaped tensors; the kernels work on the NHWC maps.  Backward keeps x, the
+    residual and the statistics the forward normalised with, and recomputes the mask of the sum from them: y is not saved."""
+
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, running_mean, running_var, training, momentum, eps, relu):
+        xh, rh = hip.to_nhwc(x.detach()), hip.to_nhwc(residual.detach())
+        w, b = weight.detach(), bias.detach()
+        y, mean, invstd = hip.batch_norm_add_forward(xh, rh, w, b, running_mean, running_var, training=training,
+                                                     momentum=momentum, eps=eps, relu=relu)
+        ctx.cfg = (training, eps, relu)
+        if training:
+            ctx.save_for_backward(xh, rh, w, b, mean, invstd)
+        else:
+            ctx.save_for_backward(xh, rh, w, b, running_mean, running_var)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        xh, rh, w, b, s0, s1 = ctx.saved_tensors
+        training, eps, relu = ctx.cfg
+        saved = (s0, s1, None, None) if training else (None, None, s0, s1)
+        nx, nr, nw, nb = ctx.needs_input_grad[:4]
+        dx, dw, db, dr = hip.batch_norm_add_backward(hip.to_nhwc(dout), xh, rh, w, b, *saved, training=training, eps=eps,
+                                                     relu=relu, need=(nx, nw, nb, nr))
+        return ((None if dx is None else dx.permute(0, 3, 1, 2)), (None if dr is None else dr.permute(0, 3, 1, 2)), dw, db,
+                None, None, None, None, None, None)
+
+
+def batch_norm_add(x, residual, weight, bias, running_mean, running_var, training, momentum=0.1, eps=1e-5, relu=True):
+    """Differentiable `relu(F.batch_norm(x) + residual)` (affine, C % 4 == 0; `relu=False`: the bare sum) on NCHW device tensors
+    of one shape: the tail of a ResNet bottleneck as one kernel pair.  The result is NCHW-shaped over channels-last memory;
+    channels-last inputs are not copied.  Statistics as in `batch_norm`: the residual does not enter them, and the running
+    statistics move in training mode whether or not a gradient is recorded."""
+    hip._dev(x), hip._dev(residual), hip._dev(weight), hip._dev(bias)
+    if x.dim() != 4 or weight.dim() != 1 or x.shape[1] != weight.shape[0]:
+        raise hip.HipError('batch_norm_add: input %s and weight %s do not fit' % (tuple(x.shape), tuple(weight.shape)))
+    if residual.shape != x.shape:
+        raise hip.HipError('batch_norm_add: residual %s does not belong to input %s' % (tuple(residual.shape), tuple(x.shape)))
+    if not training and (running_mean is None or running_var is None):
+        raise hip.HipError('batch_norm_add: eval mode needs the running statistics')
+    args = (running_mean, running_var, bool(training), float(momentum), float(eps), bool(relu))
+    if _wants_grad(x, residual, weight, bias):
+        return BatchNormAddFunction.apply(x, residual, weight, bias, *args)
+    y = hip.batch_norm_add_forward(hip.to_nhwc(x), hip.to_nhwc(residual), weight.detach(), bias.detach(), running_mean,
+                                   running_var, training=args[2], momentum=args[3], eps=args[4], relu=args[5])[0]
+    return y.permute(0, 3, 1, 2)
+
+
 class ConfFusionFunction(torch.autograd.Function):
     """out[b] = sum_m exp(clamp(conf[b*M + m], -6, 4)) / S[b] * value[b*M + m] on NCHW-shaped tensors; the kernels work on the
     NHWC maps, which are all backward keeps: the weights and `out` are recomputed."""

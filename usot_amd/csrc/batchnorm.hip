@@ -18,6 +18,11 @@
 //     save_invstd, the running statistics, dgamma and dbeta.  Then a grid-stride loop over the steps.
 // The ReLU mask of the backward pass is recomputed: bn_pre() is the one place `pre` is formed, contraction is off inside it, and
 // mean / invstd reach the backward pass as the very floats the forward used (save_*, or inv_std() of the running variance).
+//
+// The residual form (usot_bn_add_desc: y = act(pre + res), a bottleneck's bn3 - add - ReLU) is the RES = true instantiation of
+// (2) and of bn_bwd_sums_f32: one more 16-byte load per row next to x, s = pre + res formed in bn_pre_add() alone, dres = dy'
+// stored next to dx.  The statistics do not see the residual (bn_stats_f32 as it is).  RES = false takes the BnK argument block
+// and compiles every residual line away: the plain entry points keep their instruction streams.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
@@ -42,6 +47,14 @@ struct BnK {
     float eps, momentum;
 };
 
+// the argument block of the residual instantiations: BnK as it is, then the residual and its gradient
+struct BnAddK : BnK {
+    const float *res;
+    float *dres;
+};
+template <bool RES> struct Args { typedef BnK type; };
+template <> struct Args<true> { typedef BnAddK type; };
+
 __device__ __forceinline__ float inv_std(float var, float eps) { return 1.0f / sqrtf(var + eps); }
 
 // xhat and the pre-activation: the same three roundings wherever it is called
@@ -51,6 +64,14 @@ __device__ __forceinline__ float bn_pre(float x, float mean, float invstd, float
     const float c = x - mean;
     xhat = c * invstd;
     return fmaf(xhat, g, b);
+}
+
+// the pre-activation of the residual form, s = pre + res: one float32 add behind bn_pre's three roundings, never contracted
+__device__ __forceinline__ float bn_pre_add(float x, float mean, float invstd, float g, float b, float res, float &xhat)
+{
+#pragma clang fp contract(off)
+    const float pre = bn_pre(x, mean, invstd, g, b, xhat);
+    return pre + res;
 }
 
 __device__ __forceinline__ int slice_begin(int steps, int slices, int s) { return (int)((long)steps * s / slices); }
@@ -148,7 +169,8 @@ __global__ __launch_bounds__(256) void bn_stats_f32(const BnK p)
     }
 }
 
-__global__ __launch_bounds__(256) void bn_fwd_apply_f32(const BnK p)
+template <bool RES>
+__global__ __launch_bounds__(256) void bn_fwd_apply_f32(const typename Args<RES>::type p)
 {
     __shared__ double sm[4][2][CB];
     __shared__ double smn[4];
@@ -202,18 +224,22 @@ __global__ __launch_bounds__(256) void bn_fwd_apply_f32(const BnK p)
     for (int st = blockIdx.x; st < p.steps; st += gridDim.x) {
         const int k = rows_of(p.M, st, rg);
         const long off = ((long)st * R + rg) * p.C + c;
-        f32x4 v[RPT];
+        f32x4 v[RPT], r[RPT];
 #pragma unroll
         for (int j = 0; j < RPT; ++j)
-            if (j < k) v[j] = *(const f32x4 *)(p.x + off + (long)j * RG * p.C);
+            if (j < k) {
+                v[j] = *(const f32x4 *)(p.x + off + (long)j * RG * p.C);
+                if constexpr (RES) r[j] = *(const f32x4 *)(p.res + off + (long)j * RG * p.C);
+            }
 #pragma unroll
         for (int j = 0; j < RPT; ++j)
             if (j < k) {
                 f32x4 o;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    float xh;
-                    const float pre = bn_pre(v[j][e], mean[e], is[e], g[e], b[e], xh);
+                    float xh, pre;
+                    if constexpr (RES) pre = bn_pre_add(v[j][e], mean[e], is[e], g[e], b[e], r[j][e], xh);
+                    else pre = bn_pre(v[j][e], mean[e], is[e], g[e], b[e], xh);
                     o[e] = p.act ? (pre > 0.f ? pre : 0.f) : pre;
                 }
                 *(f32x4 *)(p.y + off + (long)j * RG * p.C) = o;
@@ -232,7 +258,8 @@ __device__ __forceinline__ void load_stats(const BnK &p, int c, f32x4 &mean, f32
         for (int e = 0; e < 4; ++e) is[e] = inv_std(v[e], p.eps);
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_sums_f32(const BnK p)
+template <bool RES>
+__global__ __launch_bounds__(256) void bn_bwd_sums_f32(const typename Args<RES>::type p)
 {
     __shared__ float sm[RG][2][CB];
     const int t = threadIdx.x, cl = t & 15, rg = t >> 4;
@@ -248,12 +275,13 @@ __global__ __launch_bounds__(256) void bn_bwd_sums_f32(const BnK p)
         for (int st = s0; st < s1; ++st) {
             const int k = rows_of(p.M, st, rg);
             const long off = ((long)st * R + rg) * p.C + c;
-            f32x4 v[RPT], d[RPT];
+            f32x4 v[RPT], d[RPT], r[RPT];
 #pragma unroll
             for (int j = 0; j < RPT; ++j)
                 if (j < k) {
                     v[j] = *(const f32x4 *)(p.x + off + (long)j * RG * p.C);
                     d[j] = *(const f32x4 *)(p.dy + off + (long)j * RG * p.C);
+                    if constexpr (RES) r[j] = p.act ? *(const f32x4 *)(p.res + off + (long)j * RG * p.C) : d[j];   // the mask alone reads it
                 }
             f32x4 tb = {0.f, 0.f, 0.f, 0.f}, tg = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -261,8 +289,9 @@ __global__ __launch_bounds__(256) void bn_bwd_sums_f32(const BnK p)
                 if (j < k) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        float xh;
-                        const float pre = bn_pre(v[j][e], mean[e], is[e], g[e], b[e], xh);
+                        float xh, pre;
+                        if constexpr (RES) pre = bn_pre_add(v[j][e], mean[e], is[e], g[e], b[e], r[j][e], xh);
+                        else pre = bn_pre(v[j][e], mean[e], is[e], g[e], b[e], xh);
                         const float dd = (p.act && !(pre > 0.f)) ? 0.f : d[j][e];
                         tb[e] += dd;
                         tg[e] = fmaf(dd, xh, tg[e]);
@@ -287,7 +316,8 @@ __global__ __launch_bounds__(256) void bn_bwd_sums_f32(const BnK p)
     }
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_apply_f32(const BnK p)
+template <bool RES>
+__global__ __launch_bounds__(256) void bn_bwd_apply_f32(const typename Args<RES>::type p)
 {
     __shared__ float sm[4][2][CB];
     __shared__ __attribute__((aligned(16))) float co[2][CB];      // dbeta / M, dgamma / M
@@ -320,41 +350,56 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_f32(const BnK p)
         }
         __syncthreads();
     }
-    if (!p.dx) return;
+    if constexpr (RES) {
+        if (!p.dx && !p.dres) return;
+    } else {
+        if (!p.dx) return;
+    }
     const int cl = t & 15, rg = t >> 4, c = c0 + 4 * cl;
     if (c >= p.C) return;
     f32x4 mean, is, kb = {0.f, 0.f, 0.f, 0.f}, kg = {0.f, 0.f, 0.f, 0.f}, b = {0.f, 0.f, 0.f, 0.f};
     const f32x4 g = *(const f32x4 *)(p.gamma + c);
     load_stats(p, c, mean, is);
     if (p.act) b = *(const f32x4 *)(p.beta + c);
-    if (p.training) {
+    bool coeffs = p.training;
+    if constexpr (RES) coeffs = p.training && p.dx;      // dres alone: no reduction ran, and x is read for the mask only
+    if (coeffs) {
         kb = *(const f32x4 *)&co[0][4 * cl];
         kg = *(const f32x4 *)&co[1][4 * cl];
     }
     const f32x4 a = g * is;
-    const bool need_x = p.act || p.training;
+    const bool need_x = p.act || coeffs;
     for (int st = blockIdx.x; st < p.steps; st += gridDim.x) {
         const int k = rows_of(p.M, st, rg);
         const long off = ((long)st * R + rg) * p.C + c;
-        f32x4 v[RPT], d[RPT];
+        f32x4 v[RPT], d[RPT], r[RPT];
 #pragma unroll
         for (int j = 0; j < RPT; ++j)
             if (j < k) {
                 d[j] = *(const f32x4 *)(p.dy + off + (long)j * RG * p.C);
                 v[j] = need_x ? *(const f32x4 *)(p.x + off + (long)j * RG * p.C) : d[j];
+                if constexpr (RES) r[j] = p.act ? *(const f32x4 *)(p.res + off + (long)j * RG * p.C) : d[j];
             }
 #pragma unroll
         for (int j = 0; j < RPT; ++j)
             if (j < k) {
                 f32x4 o;
+                [[maybe_unused]] f32x4 m;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    float xh;
-                    const float pre = bn_pre(v[j][e], mean[e], is[e], g[e], b[e], xh);
+                    float xh, pre;
+                    if constexpr (RES) pre = bn_pre_add(v[j][e], mean[e], is[e], g[e], b[e], r[j][e], xh);
+                    else pre = bn_pre(v[j][e], mean[e], is[e], g[e], b[e], xh);
                     const float dd = (p.act && !(pre > 0.f)) ? 0.f : d[j][e];
                     o[e] = p.training ? a[e] * (dd - kb[e] - xh * kg[e]) : a[e] * dd;
+                    if constexpr (RES) m[e] = dd;
                 }
-                *(f32x4 *)(p.dx + off + (long)j * RG * p.C) = o;
+                if constexpr (RES) {
+                    if (p.dx) *(f32x4 *)(p.dx + off + (long)j * RG * p.C) = o;
+                    if (p.dres) *(f32x4 *)(p.dres + off + (long)j * RG * p.C) = m;
+                } else {
+                    *(f32x4 *)(p.dx + off + (long)j * RG * p.C) = o;
+                }
             }
     }
 }
@@ -398,6 +443,13 @@ bool misaligned(std::initializer_list<const void *> ps)
     uintptr_t a = 0;
     for (const void *q : ps) a |= (uintptr_t)q;
     return (a & 15) != 0;
+}
+
+void fill(const usot_bn_desc *d, BnK &p);
+void fill(const usot_bn_add_desc *d, BnAddK &p)
+{
+    fill(&d->bn, p);
+    p.res = d->res; p.dres = d->dres;
 }
 
 void fill(const usot_bn_desc *d, BnK &p)
@@ -458,7 +510,7 @@ extern "C" int usot_batchnorm_fwd_f32(void *stream, const usot_bn_desc *d)
         hipLaunchKernelGGL(bn_stats_f32, dim3((unsigned)p.slices, (unsigned)cb), dim3(256), 0, s, p);
         USOT_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(bn_fwd_apply_f32, dim3(apply_blocks(p, cb), (unsigned)cb), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(bn_fwd_apply_f32<false>, dim3(apply_blocks(p, cb), (unsigned)cb), dim3(256), 0, s, p);
     USOT_CHECK_LAUNCH();
     return USOT_OK;
 }
@@ -478,10 +530,56 @@ extern "C" int usot_batchnorm_bwd_f32(void *stream, const usot_bn_desc *d)
     const int cb = cblocks_of(d);
     hipStream_t s = (hipStream_t)stream;
     if (sums) {
-        hipLaunchKernelGGL(bn_bwd_sums_f32, dim3((unsigned)p.slices, (unsigned)cb), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(bn_bwd_sums_f32<false>, dim3((unsigned)p.slices, (unsigned)cb), dim3(256), 0, s, p);
         USOT_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(bn_bwd_apply_f32, dim3(d->dx ? apply_blocks(p, cb) : 1u, (unsigned)cb), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(bn_bwd_apply_f32<false>, dim3(d->dx ? apply_blocks(p, cb) : 1u, (unsigned)cb), dim3(256), 0, s, p);
+    USOT_CHECK_LAUNCH();
+    return USOT_OK;
+}
+
+extern "C" int usot_batchnorm_add_fwd_f32(void *stream, const usot_bn_add_desc *a)
+{
+    if (!a) return USOT_EINVAL;
+    const usot_bn_desc *d = &a->bn;
+    if (!bn_geometry_ok(d) || !d->x || !d->gamma || !d->beta || !d->y || !a->res) return USOT_EINVAL;
+    if (d->training ? (!d->save_mean || !d->save_invstd || !d->ws) : (!d->running_mean || !d->running_var)) return USOT_EINVAL;
+    if (misaligned({d->x, d->gamma, d->beta, d->y, d->running_mean, d->running_var, a->res, a->dres})) return USOT_EINVAL;
+    if (d->training && misaligned({d->save_mean, d->save_invstd, d->ws})) return USOT_EINVAL;
+    BnAddK p;
+    fill(a, p);
+    const int cb = cblocks_of(d);
+    hipStream_t s = (hipStream_t)stream;
+    if (d->training) {
+        hipLaunchKernelGGL(bn_stats_f32, dim3((unsigned)p.slices, (unsigned)cb), dim3(256), 0, s, (const BnK &)p);
+        USOT_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(bn_fwd_apply_f32<true>, dim3(apply_blocks(p, cb), (unsigned)cb), dim3(256), 0, s, p);
+    USOT_CHECK_LAUNCH();
+    return USOT_OK;
+}
+
+extern "C" int usot_batchnorm_add_bwd_f32(void *stream, const usot_bn_add_desc *a)
+{
+    if (!a) return USOT_EINVAL;
+    const usot_bn_desc *d = &a->bn;
+    if (!bn_geometry_ok(d) || !d->x || !d->gamma || !d->dy || !a->res || (d->act && !d->beta)) return USOT_EINVAL;
+    if (d->training ? (!d->save_mean || !d->save_invstd) : (!d->running_mean || !d->running_var)) return USOT_EINVAL;
+    if (!d->dx && !d->dgamma && !d->dbeta && !a->dres) return USOT_EINVAL;
+    const bool sums = d->dgamma || d->dbeta || (d->training && d->dx);
+    if (sums && !d->ws) return USOT_EINVAL;
+    if (misaligned({d->x, d->gamma, d->beta, d->dy, d->dx, d->dgamma, d->dbeta, d->ws, a->res, a->dres})) return USOT_EINVAL;
+    if (d->training ? misaligned({d->save_mean, d->save_invstd}) : misaligned({d->running_mean, d->running_var})) return USOT_EINVAL;
+    BnAddK p;
+    fill(a, p);
+    p.reduce = sums ? 1 : 0;
+    const int cb = cblocks_of(d);
+    hipStream_t s = (hipStream_t)stream;
+    if (sums) {
+        hipLaunchKernelGGL(bn_bwd_sums_f32<true>, dim3((unsigned)p.slices, (unsigned)cb), dim3(256), 0, s, p);
+        USOT_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(bn_bwd_apply_f32<true>, dim3(d->dx || a->dres ? apply_blocks(p, cb) : 1u, (unsigned)cb), dim3(256), 0, s, p);
     USOT_CHECK_LAUNCH();
     return USOT_OK;
 }

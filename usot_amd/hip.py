@@ -83,6 +83,11 @@ class BnDesc(C.Structure):
                 ('training', C.c_int32), ('act', C.c_int32), ('slices', C.c_int32)]
 
 
+class BnAddDesc(C.Structure):
+    """usot_bn_add_desc"""
+    _fields_ = [('bn', BnDesc), ('res', C.c_void_p), ('dres', C.c_void_p)]
+
+
 class ConfFusionDesc(C.Structure):
     """usot_conf_fusion_desc"""
     _fields_ = [('conf', C.c_void_p), ('value', C.c_void_p), ('out', C.c_void_p), ('dout', C.c_void_p), ('dconf', C.c_void_p),
@@ -251,6 +256,9 @@ def lib():
         for name in ('usot_conf_fusion_fwd_f32', 'usot_conf_fusion_bwd_f32', 'usot_box_exp_fwd_f32', 'usot_box_exp_bwd_f32'):
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
         L.usot_box_exp_ws_floats.argtypes = [C.c_void_p]
+        # BatchNorm with a residual operand (csrc/batchnorm.hip): bound like the head's operators, not listed in EXPORTS
+        for name in ('usot_batchnorm_add_fwd_f32', 'usot_batchnorm_add_bwd_f32'):
+            getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
         L.usot_box_exp_ws_floats.restype = C.c_int64
         L.PrRoIPoolingForwardGpu.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float, C.c_int]
         L.PrRoIPoolingForwardGpu.restype = None
@@ -776,6 +784,79 @@ def batch_norm_backward(dy, x_nhwc, gamma, beta, save_mean, save_invstd, running
     d.dx, d.dgamma, d.dbeta, d.ws = ptr(dx), ptr(dg), ptr(db), ptr(ws)
     check(lib().usot_batchnorm_bwd_f32(stream(), C.byref(d)), 'usot_batchnorm_bwd_f32')
     return dx, dg, db
+
+
+def bn_add_desc(*, res=None, dres=None, **bn):
+    """usot_bn_add_desc: `bn_desc(**bn)` with the residual map and its gradient; pointers are addresses (or None)"""
+    d = BnAddDesc()
+    d.bn = bn_desc(**bn)
+    d.res, d.dres = res or None, dres or None
+    return d
+
+
+def batch_norm_add_forward(x_nhwc, res_nhwc, gamma, beta, running_mean, running_var, *, training, momentum=0.1, eps=1e-5,
+                           relu=True, slices=0):
+    """BatchNorm2d of a dense NHWC map [..., C], C % 4 == 0, plus a residual map of the same shape, and the ReLU behind the sum
+    (a bottleneck's tail) -> (y, save_mean, save_invstd).  Statistics and running statistics as in `batch_norm_forward`: the
+    residual does not enter them."""
+    what = 'batch_norm_add_forward'
+    M, Cc = _bn_map(what, x_nhwc)
+    _bn_map(what, res_nhwc, Cc)
+    if res_nhwc.shape != x_nhwc.shape:
+        raise HipError('%s: residual %s does not belong to input %s' % (what, tuple(res_nhwc.shape), tuple(x_nhwc.shape)))
+    d = bn_add_desc(M=M, C=Cc, eps=eps, momentum=momentum, training=training, act=ACT_RELU if relu else ACT_NONE, slices=slices,
+                    x=x_nhwc.data_ptr(), res=res_nhwc.data_ptr(), gamma=_bn_vec(what, 'gamma', gamma, Cc),
+                    beta=_bn_vec(what, 'beta', beta, Cc))
+    if running_mean is not None or not training:
+        d.bn.running_mean = _bn_vec(what, 'running_mean', running_mean, Cc)
+    if running_var is not None or not training:
+        d.bn.running_var = _bn_vec(what, 'running_var', running_var, Cc)
+    y = torch.empty(x_nhwc.shape, device=x_nhwc.device, dtype=torch.float32)
+    d.bn.y = y.data_ptr()
+    mean = invstd = ws = None
+    if training:
+        mean = torch.empty((Cc,), device=x_nhwc.device, dtype=torch.float32)
+        invstd = torch.empty((Cc,), device=x_nhwc.device, dtype=torch.float32)
+        ws = _bn_ws(d.bn, x_nhwc.device)
+        d.bn.save_mean, d.bn.save_invstd, d.bn.ws = mean.data_ptr(), invstd.data_ptr(), ws.data_ptr()
+    check(lib().usot_batchnorm_add_fwd_f32(stream(), C.byref(d)), 'usot_batchnorm_add_fwd_f32')
+    return y, mean, invstd
+
+
+def batch_norm_add_backward(dy, x_nhwc, res_nhwc, gamma, beta, save_mean, save_invstd, running_mean, running_var, *, training,
+                            eps=1e-5, relu=True, need=(True, True, True, True), slices=0):
+    """Gradients of `batch_norm_add_forward` -> (dx | None, dgamma | None, dbeta | None, dres | None), the ones `need` asks for
+    (at least one).  dy, x_nhwc and res_nhwc are dense NHWC maps of one shape; the statistics as in `batch_norm_backward`.  The
+    mask of the ReLU is recomputed from x and the residual, not read from y."""
+    what = 'batch_norm_add_backward'
+    M, Cc = _bn_map(what, x_nhwc)
+    _bn_map(what, dy, Cc)
+    _bn_map(what, res_nhwc, Cc)
+    if dy.shape != x_nhwc.shape:
+        raise HipError('%s: grad_output %s does not belong to input %s' % (what, tuple(dy.shape), tuple(x_nhwc.shape)))
+    if res_nhwc.shape != x_nhwc.shape:
+        raise HipError('%s: residual %s does not belong to input %s' % (what, tuple(res_nhwc.shape), tuple(x_nhwc.shape)))
+    need_x, need_g, need_b, need_r = (bool(v) for v in need)
+    if not (need_x or need_g or need_b or need_r):
+        raise HipError('%s: no gradient is asked for' % what)
+    d = bn_add_desc(M=M, C=Cc, eps=eps, training=training, act=ACT_RELU if relu else ACT_NONE, slices=slices,
+                    x=x_nhwc.data_ptr(), res=res_nhwc.data_ptr(), dy=dy.data_ptr(), gamma=_bn_vec(what, 'gamma', gamma, Cc))
+    if relu:
+        d.bn.beta = _bn_vec(what, 'beta', beta, Cc)
+    if training:
+        d.bn.save_mean = _bn_vec(what, 'save_mean', save_mean, Cc)
+        d.bn.save_invstd = _bn_vec(what, 'save_invstd', save_invstd, Cc)
+    else:
+        d.bn.running_mean = _bn_vec(what, 'running_mean', running_mean, Cc)
+        d.bn.running_var = _bn_vec(what, 'running_var', running_var, Cc)
+    dx = torch.empty(x_nhwc.shape, device=dy.device, dtype=torch.float32) if need_x else None
+    dr = torch.empty(x_nhwc.shape, device=dy.device, dtype=torch.float32) if need_r else None
+    dg = torch.empty((Cc,), device=dy.device, dtype=torch.float32) if need_g else None
+    db = torch.empty((Cc,), device=dy.device, dtype=torch.float32) if need_b else None
+    ws = _bn_ws(d.bn, dy.device) if need_g or need_b or (training and need_x) else None
+    d.bn.dx, d.bn.dgamma, d.bn.dbeta, d.bn.ws, d.dres = ptr(dx), ptr(dg), ptr(db), ptr(ws), ptr(dr)
+    check(lib().usot_batchnorm_add_bwd_f32(stream(), C.byref(d)), 'usot_batchnorm_add_bwd_f32')
+    return dx, dg, db, dr
 
 
 def conf_fusion_desc(*, B, M, P, C, conf=None, value=None, out=None, dout=None, dconf=None, dvalue=None):

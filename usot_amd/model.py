@@ -100,5 +100,5 @@ class USOT(USOT_):
         super().__init__(mem_size=settings['mem_size'], pr_pool=settings['pr_pool'],
                          search_size=255, score_size=25, maximum_batch=16, sf_size=25)
         self.features = BackboneSlots()
-        self.neck = NeckSlots(1024, 256)
+        self.neck = NeckSlots(1024, 256, pr_pool=settings['pr_pool'])
         self.connect_model = HeadSlots(256, 4)

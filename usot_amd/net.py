@@ -1,16 +1,17 @@
 """Parameter tree of the USOT Siamese tracker, state-dict compatible with the reference.
 
-Nothing in this file computes.  The classes below only *hold* tensors under the
-same names the reference registers them (444 state-dict keys, see
+The classes below hold tensors under the same names the reference registers them (444 state-dict keys, see
 reference lib/models/models.py:298-306, modules.py:61-135, connect.py:12-74,
 104-121, 160-219, 284-292) and record each convolution's geometry so that
-`usot_amd.engine` can lower the graph to HIP launches.  Calling `forward` on a
-holder raises: there is deliberately no torch fallback for the tensor math.
-The exceptions are `GroupDWSlots.forward`, `ConvSlot.forward` and `NormSlot.forward` (with `conv_norm`, which chains the
-latter two over one conv - BN [- ReLU] holder), and the head's holders built from them - `EncoderSlots.forward`,
-`ConfFusionSlots.forward` and `HeadSlots.forward` (the reference's `matrix`, `Conf_Fusion` and `box_tower_reg`) - which hand
-their tensors to the differentiable HIP bindings of `usot_amd.autograd` (device tensors only).  The neck, the backbone and the
-whole model still raise.
+`usot_amd.engine` can lower the graph to HIP launches.  There is deliberately no torch fallback for the tensor math.
+Every holder's `forward` hands its tensors to the differentiable HIP bindings of `usot_amd.autograd` (device tensors only):
+`GroupDWSlots`, `ConvSlot` and `NormSlot` (with `conv_norm`, which chains the latter two over one conv - BN [- ReLU] holder),
+the head's holders built from them - `EncoderSlots`, `ConfFusionSlots` and `HeadSlots` (the reference's `matrix`, `Conf_Fusion`
+and `box_tower_reg`) - and the backbone and the neck: `BottleneckSlots` (its tail bn3 - add - ReLU is one kernel pair,
+`autograd.batch_norm_add`), `ResNetPlus2Slots`, `BackboneSlots` and `NeckSlots` (`Bottleneck`, `ResNet_plus2`, `ResNet50`,
+`AdjustLayer`).  The stem (conv1 - bn1 - ReLU - max-pool) runs frozen, as the reference's recipe always runs it: its own
+gradients are not built.  Only the whole model's `forward` (usot_amd/model.py) still raises.  The inference engine does not
+come through any `forward` here: it keeps lowering the folded graph.
 """
 import torch
 import torch.nn as nn
@@ -59,13 +60,14 @@ class NormSlot(nn.Module):
         self.register_buffer('running_var', torch.ones(c))
         self.register_buffer('num_batches_tracked', torch.tensor(0, dtype=torch.long))
 
-    def forward(self, x, relu=False):
+    def forward(self, x, relu=False, residual=None):
         """nn.BatchNorm2d (and, with `relu`, the ReLU behind it) of an NCHW device tensor; differentiable
-        (usot_amd.autograd.batch_norm).  self.training chooses batch or running statistics; a training-mode call moves the
+        (usot_amd.autograd.batch_norm).  With a `residual` of x's shape the result is [relu](bn(x) + residual), one kernel
+        (usot_amd.autograd.batch_norm_add).  self.training chooses batch or running statistics; a training-mode call moves the
         running statistics and counts itself in num_batches_tracked, all on the device."""
         from . import autograd
-        y = autograd.batch_norm(x, self.weight, self.bias, self.running_mean, self.running_var, self.training, self.momentum,
-                                self.eps, relu)
+        args = (self.weight, self.bias, self.running_mean, self.running_var, self.training, self.momentum, self.eps, relu)
+        y = autograd.batch_norm(x, *args) if residual is None else autograd.batch_norm_add(x, residual, *args)
         if self.training:
             self.num_batches_tracked.add_(1)
         return y
@@ -110,6 +112,15 @@ class BottleneckSlots(nn.Module):
         self.bn3 = NormSlot(planes * 4)
         self.downsample = downsample
 
+    def forward(self, x):
+        """reference modules.py:37-58 on an NCHW device tensor, differentiable, in the module's mode: conv1 - bn1 - ReLU,
+        conv2 - bn2 - ReLU, conv3, then relu(bn3(.) + residual) as one kernel, the residual being x or the downsample's
+        conv - BN of it."""
+        out = self.bn1(self.conv1(x), relu=True)
+        out = self.bn2(self.conv2(out), relu=True)
+        residual = x if self.downsample is None else conv_norm(self.downsample, x)
+        return self.bn3(self.conv3(out), relu=True, residual=residual)
+
 
 class ResNetPlus2Slots(nn.Module):
     """reference modules.py:61-135 with layers=[3,4,6,3], used_layers=[3]."""
@@ -138,6 +149,42 @@ class ResNetPlus2Slots(nn.Module):
             blks.append(BottleneckSlots(self.inplanes, planes, dilation=dilation))
         return _seq(*blks)
 
+    def _stem(self):
+        """conv1 with bn1's running statistics folded in, float64 as `engine.Weights` folds it: the [147][64] bank and the bias
+        that carries the STEM_MU offset of the stem kernel.  Cached on the versions of the five tensors."""
+        from .engine import Weights
+        ts = (self.conv1.weight, self.bn1.weight, self.bn1.bias, self.bn1.running_mean, self.bn1.running_var)
+        key = tuple((t.data_ptr(), t._version) for t in ts)
+        if getattr(self, '_stem_key', None) != key:
+            w, g, b, rm, rv = (t.detach().double().cpu() for t in ts)
+            s = g / torch.sqrt(rv + self.bn1.eps)
+            bank = (w * s.view(-1, 1, 1, 1)).permute(1, 2, 3, 0)
+            mu = torch.tensor(Weights.STEM_MU, dtype=torch.float64).view(3, 1, 1, 1)
+            dev = self.conv1.weight.device
+            self._stem_fold = (bank.reshape(147, 64).float().contiguous().to(dev),
+                               (b - rm * s + (bank * mu).sum((0, 1, 2))).float().to(dev))
+            self._stem_key = key
+        return self._stem_fold
+
+    def forward(self, x):
+        """reference modules.py:137-151 on an NCHW device image -> ([x_, p1, p2], p3), NCHW-shaped over channels-last memory.
+        layer1-3 are differentiable in their own modes.  The stem runs as the reference's recipe always runs it
+        (train_usot.py: stem parameters frozen, bn1.eval()): the folded stem kernel, then the max-pool kernel, no graph."""
+        from . import hip
+        from .engine import Weights
+        hip._dev(x)
+        if self.bn1.training or x.requires_grad or any(p.requires_grad for p in (self.conv1.weight, self.bn1.weight, self.bn1.bias)):
+            raise NotImplementedError("the stem's gradients (7x7 conv with Cin = 3, max-pool) are not built: run the "
+                                      'reference recipe - bn1.eval(), stem parameters frozen (conv1.weight, bn1.weight and '
+                                      'bn1.bias without requires_grad), an image that does not require grad')
+        bank, bias = self._stem()
+        stem = hip.stem_conv(x.detach().contiguous(), bank, bias, Weights.STEM_MU)
+        x_ = stem.permute(0, 3, 1, 2)
+        p1 = self.layer1(hip.maxpool3x3s2(stem).permute(0, 3, 1, 2))
+        p2 = self.layer2(p1)
+        p3 = self.layer3(p2)
+        return [x_, p1, p2], p3
+
 
 class BackboneSlots(nn.Module):
     """reference backbones.py:12-22 — adds the extra `features.` level to the keys."""
@@ -146,13 +193,34 @@ class BackboneSlots(nn.Module):
         super().__init__()
         self.features = ResNetPlus2Slots()
 
+    def forward(self, x):
+        """reference backbones.py:20-22 -> (x_stages, x)"""
+        x_stages, x = self.features(x)
+        return x_stages, x
+
 
 class NeckSlots(nn.Module):
     """reference connect.py:284-292 (AdjustLayer)."""
 
-    def __init__(self, cin=1024, cout=256):
+    def __init__(self, cin=1024, cout=256, pr_pool=False):
         super().__init__()
         self.downsample = _seq(ConvSlot(cin, cout, 1), NormSlot(cout))
+        self.pr_pool = bool(pr_pool)         # the reference registers a parameter-free PrRoIPool2D(7, 7, 1.0) here: no key
+
+    def forward(self, x, crop=False, pr_pool=False, bbox=None):
+        """reference connect.py:294-314 on an NCHW device tensor, differentiable, in the module's mode: the 1x1 conv - BN;
+        with `crop` also the [4:-4] centre (a view), or with `pr_pool` the 7 x 7 PrRoIPool at scale 1.0 of `bbox` [N, 4]
+        (one box per map; the batch index is prepended on the device)."""
+        x_ori = conv_norm(self.downsample, x)
+        if not crop:
+            return x_ori
+        if not pr_pool:
+            return x_ori, x_ori[:, :, 4:-4, 4:-4]
+        if not self.pr_pool:
+            raise AttributeError('AdjustLayer was built without pr_pool')
+        from lib.models.prroi_pool.functional import prroi_pool2d
+        index = torch.arange(0, x.shape[0], device=x.device, dtype=torch.float32).view(-1, 1)
+        return x_ori, prroi_pool2d(x_ori, torch.cat((index, bbox), dim=1), 7, 7, 1.0)
 
 
 class EncoderSlots(nn.Module):
