@@ -74,8 +74,8 @@ def sweep_tiles():
 TILES = conftest.tile_params(sweep_tiles())
 
 
-def report(family, what, worst):
-    print('tile_edges %s %s: worst rel_err %.3g' % (family, what, worst))
+def report(family, what, worst, label='worst rel_err'):
+    print('tile_edges %s %s: %s %.3g' % (family, what, label, worst))
 
 
 def _act(v, act):
@@ -307,14 +307,15 @@ def _conv_bank(c, tile, w, b):
 
 
 def _conv_setup(c, tile, x, bank, *, Cout, KH=1, KW=1, pad=(0, 0), res=None, act=NONE, ksplit=1, y_nchw=False, ovf=None, y=None,
-                xshape=None, **fields):
-    """descriptor of one usot_conv2d_f32 launch (stride 1, dilation 1) -> (desc, y, ws, first ticket word); the split-K workspace
-    holds the NaN pattern in its slabs and zero ticket words.  `y`: an output the caller made (a channel slice, group gaps: the
-    caller checks it, prefill included); `xshape`: (N, H, W, Cin) of one group when x is a flat buffer of several; `fields`: the
-    remaining descriptor fields, passed through (act2, act_split, y_cstride, y_coff, res_cstride, res_coff, groups, *_gs)."""
+                xshape=None, stride=1, dil=(1, 1), **fields):
+    """descriptor of one usot_conv2d_f32 launch (stride 1, dilation 1 unless given) -> (desc, y, ws, first ticket word); the
+    split-K workspace holds the NaN pattern in its slabs and zero ticket words.  `y`: an output the caller made (a channel slice,
+    group gaps: the caller checks it, prefill included); `xshape`: (N, H, W, Cin) of one group when x is a flat buffer of several;
+    `fields`: the remaining descriptor fields, passed through (act2, act_split, y_cstride, y_coff, res_cstride, res_coff, groups,
+    *_gs)."""
     wd, sc, bd, frag = bank
     N, H, W_, Cin = xshape or x.shape
-    OH, OW = H + 2 * pad[0] - (KH - 1), W_ + 2 * pad[1] - (KW - 1)
+    OH, OW = (H + 2 * pad[0] - dil[0] * (KH - 1) - 1) // stride + 1, (W_ + 2 * pad[1] - dil[1] * (KW - 1) - 1) // stride + 1
     M = N * OH * OW
     G = fields.get('groups', 1)
     if y is None:
@@ -326,7 +327,7 @@ def _conv_setup(c, tile, x, bank, *, Cout, KH=1, KW=1, pad=(0, 0), res=None, act
         ws = c.out((tick + G * ((M + 15) // 16) * ((Cout + 31) // 32),))
         ws[tick:].zero_()
     d = hip.conv_desc(x.data_ptr(), wd.data_ptr(), bd.data_ptr(), y.data_ptr(), N=N, H=H, W=W_, Cin=Cin, OH=OH, OW=OW, Cout=Cout, KH=KH, KW=KW,
-                      pad=pad, res=res.data_ptr() if res is not None else None, act=act, tile=tile, ksplit=ksplit,
+                      stride=stride, pad=pad, dil=dil, res=res.data_ptr() if res is not None else None, act=act, tile=tile, ksplit=ksplit,
                       ws=ws.data_ptr() if ws is not None else None, y_nchw=int(y_nchw), w_frag=frag,
                       w_scale=sc.data_ptr() if sc is not None else None, ovf=ovf.data_ptr() if ovf is not None else None, **fields)
     return d, y, ws, tick
