@@ -2,7 +2,9 @@
 """Builds usot_amd/csrc/alt/lib_<name>.so: the library with ONE translation unit recompiled under extra -D flags (timing /
 ablation builds; usot_amd/csrc/alt/ is git-ignored but travels to the GPU box).  The other objects are the up-to-date ones
 of the normal build.  A variant whose record (lib_<name>.json: source tree, unit, flags) matches is not built again.
-    python scripts/build_variant.py <name> <file.hip> -DUSOT_ABL_NOW [...]"""
+    python scripts/build_variant.py <name> <file.hip> -DUSOT_ABL_NOW [...]
+The unit is the .hip file even where the switch stands in one of its headers: USOT_ABL_* / USOT_TRACE are read by csrc/conv_f32_v3.h,
+USOT_WS_* / USOT_WSTAT_* by csrc/lab/conv_f32_wstream.h / conv_f32_wstat.h (with -DUSOT_EXPERIMENTS), all built as conv_igemm.hip."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Where a batch-1 k-step goes: builds the library with -DUSOT_TRACE (s_memtime stamps in one workgroup's
-consumer wave 0 and producer wave 0 of conv_igemm_f32_v3 / v4, written to the split-K workspace), runs layer3's
+consumer wave 0 and producer wave 0 of conv_igemm_f32_v3 (usot_amd/csrc/conv_f32_v3.h), written to the split-K workspace), runs layer3's
 3x3 dilated conv (M = 961, N = 256, K = 2304) on the given tiles and prints the median phase lengths in
 shader-clock cycles.   python scripts/trace_kstep.py 41 53 54"""
 import ctypes as C, glob, os, subprocess, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-# USOT_TRACE_LIB: a library already built with -DUSOT_TRACE (conv_igemm.hip is the only file that reads the macro)
+# USOT_TRACE_LIB: a library already built with -DUSOT_TRACE (conv_igemm.hip is the only unit that reads the macro: its header conv_f32_v3.h)
 trace_lib = os.environ.get('USOT_TRACE_LIB') or os.path.join(ROOT, 'gpurun_out', 'libusot_hip_trace.so')
 if not os.environ.get('USOT_TRACE_LIB'):
     os.makedirs(os.path.dirname(trace_lib), exist_ok=True)

@@ -152,3 +152,40 @@ def test_default_library_holds_exactly_the_routed_conv_tiles(libpath):
     lp_built = {t for t in range(1, L.usot_conv_bf16_tile_count() + 1) if L.usot_conv_bf16_tile_built(t)}
     assert lp_built == lp_routed, (sorted(lp_built - lp_routed), sorted(lp_routed - lp_built))
     assert os.path.getsize(libpath) < 4 * 1024 * 1024                # 8.5 MB with the experiments
+
+
+def _conv_igemm_deps(extra):
+    """files `conv_igemm.hip` includes (host pass, -M: no code generation), under the library's flags + `extra`"""
+    import subprocess
+    unit = 'conv_igemm.hip'
+    flags = [f for f in build.FLAGS if f != '-DUSOT_EXPERIMENTS'] + build.FILE_FLAGS.get(unit, [])
+    p = subprocess.run([build._hipcc()] + flags + extra + ['--cuda-host-only', '-M', os.path.join(build.CSRC, unit)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE)
+    assert p.returncode == 0, p.stderr.decode(errors='replace')
+    return {os.path.normpath(w) for w in p.stdout.decode().replace('\\\n', ' ').split() if w.endswith('.h')}
+
+
+def test_default_build_of_the_fp32_conv_unit_reads_no_lab_header():
+    """The kernel families with no routed tile (stream-K, weight-streaming, weight-stationary) live in csrc/lab/: the default build
+    of conv_igemm.hip includes none of those headers, an experiments build includes every one of them."""
+    import glob
+    lab = {os.path.normpath(f) for f in glob.glob(os.path.join(build.CSRC, 'lab', '*.h'))}
+    assert len(lab) >= 3
+    default = _conv_igemm_deps([])
+    assert os.path.normpath(os.path.join(build.CSRC, 'conv_f32_v3.h')) in default           # the list does name the unit's own headers
+    assert not [f for f in default if os.sep + 'lab' + os.sep in f], sorted(default)
+    assert lab <= _conv_igemm_deps(['-DUSOT_EXPERIMENTS'])
+
+
+def test_lab_headers_are_part_of_the_header_set_and_of_the_tree_key(tmp_path, monkeypatch):
+    import glob
+    lab = sorted(glob.glob(os.path.join(build.CSRC, 'lab', '*.h')))
+    assert lab and set(lab) <= set(build.headers())
+    a = build.csrc_tree()
+    # the same header set with one lab header's content changed -> another key
+    changed = tmp_path / os.path.basename(lab[0])
+    with open(lab[0]) as f:
+        changed.write_text(f.read() + '// one more line\n')
+    real = build.headers
+    monkeypatch.setattr(build, 'headers', lambda: [str(changed) if h == lab[0] else h for h in real()])
+    assert build.csrc_tree() != a

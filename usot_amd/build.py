@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, 'csrc')
 INCLUDE = os.path.join(os.path.dirname(HERE), 'include')
 LIB = os.path.join(CSRC, 'libusot_hip.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-I' + INCLUDE, '-I' + CSRC]
-# USOT_EXPERIMENTS=1 in the environment: compile the experimental conv tiles too (csrc/conv_igemm.hip / conv_bf16.hip: the ids no
+# USOT_EXPERIMENTS=1 in the environment: compile the experimental conv tiles too (csrc/conv_igemm.hip with csrc/lab/*.h, conv_bf16.hip: the ids no
 # tuning table routes - lab notebook A.3); the default library holds the routed tiles only.  Part of csrc_tree(): the two builds
 # never share counters or objects silently.
 EXPERIMENTS = os.environ.get('USOT_EXPERIMENTS', '0') == '1'
@@ -28,12 +28,12 @@ INFO = os.path.join(CSRC, 'build_info.json')      # written by build(): what the
 
 
 def csrc_tree():
-    """Content hash of everything libusot_hip.so is built from (csrc/*.hip, csrc/*.h, include/*.h, this file's flags): the
+    """Content hash of everything libusot_hip.so is built from (csrc/*.hip, headers(), this file's flags): the
     key that ties a committed counter file (profiles/pmc_*.json: `_meta.csrc_tree`) to the kernels it was measured on.  The
     GPU box has no .git, so this is a hash of file contents, not `git rev-parse HEAD:usot_amd/csrc`."""
     import hashlib
     h = hashlib.sha256()
-    files = sources() + sorted(glob.glob(os.path.join(CSRC, '*.h'))) + sorted(glob.glob(os.path.join(INCLUDE, '*.h')))
+    files = sources() + headers()
     for f in files:
         h.update(os.path.basename(f).encode() + b'\0')
         with open(f, 'rb') as fh:
@@ -77,12 +77,18 @@ def sources():
     return sorted(glob.glob(os.path.join(CSRC, '*.hip')))
 
 
+def headers():
+    """Every header a translation unit may include, sorted within each directory: csrc/*.h, csrc/lab/*.h (the kernel families only an
+    experiments build compiles) and include/*.h.  The lab headers count in BOTH builds - for the staleness check and for
+    csrc_tree() - although the default build never reads them: one rule, no per-build header list."""
+    return [f for d in (CSRC, os.path.join(CSRC, 'lab'), INCLUDE) for f in sorted(glob.glob(os.path.join(d, '*.h')))]
+
+
 def is_stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = (sources() + glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(INCLUDE, '*.h'))
-            + [os.path.abspath(__file__)])               # FLAGS / FILE_FLAGS live in this file
+    deps = sources() + headers() + [os.path.abspath(__file__)]        # FLAGS / FILE_FLAGS live in this file
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -104,7 +110,7 @@ def build(force=False, verbose=False):
     cc = _hipcc()
     objs = []
     procs = []
-    hdrs = glob.glob(os.path.join(CSRC, '*.h')) + glob.glob(os.path.join(INCLUDE, '*.h')) + [os.path.abspath(__file__)]
+    hdrs = headers() + [os.path.abspath(__file__)]
     for src in sources():
         obj = src[:-4] + '.o'
         objs.append(obj)

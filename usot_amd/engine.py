@@ -337,7 +337,7 @@ class Builder:
         if force_ks is not None:
             ksplit = force_ks
         ws = None
-        # 'split16_f32': the producer / consumer tiles of the long reductions run on their split-fp16 twins (csrc/conv_igemm.hip, PF = 4)
+        # 'split16_f32': the producer / consumer tiles of the long reductions run on their split-fp16 twins (csrc/conv_f32_v3.h, PF = 4)
         if (self.opt['split16_f32'] and k >= self.opt['split16_min_k'] and m >= self.opt['split16_min_m'] and pc.cin % 64 == 0
                 and ttile in SPLIT16_TILES):
             ttile = SPLIT16_TILES[ttile]
@@ -1349,7 +1349,7 @@ DEFAULT_OPTIONS = {
     'panel_min_panels': 192,
     # OPT-IN fast mode of the fp32 frame (default: exact fp32 products on v_mfma_f32_16x16x4_f32, the reference's arithmetic).  True:
     # fp32 convolutions with K >= split16_min_k on the producer / consumer tiles run on the split-fp16 form of the tile (every operand
-    # as hi + lo fp16 - 22 significant bits - three fp16 MFMAs per product block, fp32 accumulation: csrc/conv_igemm.hip PF = 4 | 5):
+    # as hi + lo fp16 - 22 significant bits - three fp16 MFMAs per product block, fp32 accumulation: csrc/conv_f32_v3.h PF = 4 | 5):
     # the frame 0.84 -> 0.68 ms at the same 1e-4 parity.  Operands must stay below 8 188 in magnitude; a launch that sees one beyond it
     # says so in a sticky device word (usot_conv_desc.ovf) and the engine re-plans on the exact tiles and runs the call / frame again
     # (Engine._to_exact, Session._rerun_exact) - the mode never returns a wrong finite number and never fails mid-video
@@ -1499,7 +1499,7 @@ DEFAULT_OPTIONS = {
     # shortcut conv of layer2.0 already fills one round, a second workgroup per CU stretches every k-step by more than the halved loop saves
     'defer_split_res_f32': {},
     'defer_split_f32': {(961, 256, 2304): (55, 2), (1089, 256, 2304): (55, 2), (961, 128, 1152): (53, 2), (1089, 128, 1152): (53, 2)},
-    # ... and the (tile, ksplit) those deferred launches use when split16_f32 is on (filter-DMA tiles, csrc/conv_igemm.hip PF = 5)
+    # ... and the (tile, ksplit) those deferred launches use when split16_f32 is on (filter-DMA tiles, csrc/conv_f32_v3.h PF = 5)
     'defer_split_s16': {(961, 256, 2304): (106, 2), (1089, 256, 2304): (106, 2), (961, 128, 1152): (111, 2), (1089, 128, 1152): (111, 2)},
 }
 ENV_SWITCHES = {      # environment variable -> (option, parser)

@@ -426,7 +426,7 @@ def tile_table_lp():
 
 # ------------------------------------------------------------------ tensor-level wrappers
 
-SPLIT16_X_SCALE = 8.0      # csrc/conv_igemm.hip (PF = 4): the activations are split as hi + lo fp16 of 8 x
+SPLIT16_X_SCALE = 8.0      # csrc/conv_f32_v3.h (PF = 4): the activations are split as hi + lo fp16 of 8 x
 
 
 def split16_pack(w):
