@@ -2,7 +2,8 @@
 """Where a batch-1 k-step goes: builds the library with -DUSOT_TRACE (s_memtime stamps in one workgroup's
 consumer wave 0 and producer wave 0 of conv_igemm_f32_v3 (usot_amd/csrc/conv_f32_v3.h), written to the split-K workspace), runs layer3's
 3x3 dilated conv (M = 961, N = 256, K = 2304) on the given tiles and prints the median phase lengths in
-shader-clock cycles.   python scripts/trace_kstep.py 41 53 54"""
+shader-clock cycles, and the start-up of the
+producer wave (kernel entry -> first loads issued -> first barrier -> first k-step).   python scripts/trace_kstep.py 41 53 54"""
 import ctypes as C, glob, os, subprocess, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,7 +30,13 @@ for tile in [int(v) for v in sys.argv[1:]] or [41, 53]:
     for _ in range(2):
         hip.check(L.usot_conv2d_f32(hip.stream(), C.byref(d)))
     torch.cuda.synchronize()
-    t = (ws.cpu().numpy().astype(np.int64) & 0xffffffff).reshape(64, 8)[2:34]
+    full = (ws.cpu().numpy().astype(np.int64) & 0xffffffff).reshape(64, 8)
+    t = full[2:34]
+    # start-up of producer wave 0 (row 60: kernel entry, the x and w loads of k-tiles 0 and 1 issued, first barrier passed; the first
+    # k-step starts at row 0's slot 4): cycles from entry, 32-bit counter differences
+    e = full[60, 0]
+    su = [int((v - e) & 0xffffffff) for v in (full[60, 1], full[60, 2], full[0, 4])]
+    print('%-44s start-up: entry -> first loads issued %5d, -> first barrier passed %5d, -> first k-step %5d cycles' % (hip.tile_name(tile), su[0], su[1], su[2]))
     med = lambda a: int(np.median(a))
     print('%-44s k-step %5d | consumer: MFMA phase %4d, barrier wait %4d | producer: wait for loads %4d, convert + LDS stores %4d, loads %4d, barrier wait %4d' % (
         hip.tile_name(tile), med(np.diff(t[:, 0])), med(t[:, 1] - t[:, 0]), med(t[:, 2] - t[:, 1]),

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include "usot_hip.h"
 #include "common.h"
+#include "fastdiv.h"
 
 namespace {
 
@@ -15,37 +16,95 @@ typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2_t __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 
-struct ConvK {
+// What a kernel reads between its entry and its first k-step, in ONE contiguous block of five 64-byte lines at the front of a problem:
+// the kernels fetch it with five s_load_dwordx16 issued together and waited for once (conv_pro_fetch below) instead of a field at a
+// time where each is first used - ten dependent scalar-memory round trips in front of the first activation load on the parent of
+// this layout (docs/LAB_NOTEBOOK.md A.9).  fill_params and the launcher fill it, the division constants (fastdiv.h) included: every
+// quotient of the index prologue has a divisor that is known when the launch is prepared.
+struct alignas(64) ConvPro {
     const float *x, *w, *bias, *res;
     float *y, *ws;
-    int N, H, W, Cin, OH, OW, Cout;
-    int KH, KW, stride, pad_h, pad_w, dil_h, dil_w;
-    int y_cstride, y_coff, res_cstride, res_coff, y_nchw;
-    int act, act2, act_split;
-    int groups;
-    long x_gs, w_gs, b_gs, y_gs, r_gs;
-    int ksplit;
-    int combine;                        // split-K: 1 = last-arriver combine inside the launch, 0 = second launch
-    int M, K, KT, cchunks, MT, NT, P;   // P = OH*OW
-    int vec_store;
-    int pr;                             // weight-stationary tiles: pixel ranges per (group, 32-channel block)
+    const int *n_dyn;                   // v3 tiles: nullptr, or a device word with a run-time image count (usot_conv_desc.n_dyn): images
+                                        // [0, clamp(*n_dyn - n_first, 0, N)) of this problem are live, the rest is neither read nor written
     const float *wscale;                // split-fp16 tiles (PF = 4): 1 / (filter row scale x activation scale) per output channel
+    long x_gs, w_gs, b_gs, y_gs, r_gs;
+    int N, H, W, Cin, OW, Cout;
+    int stride, pad_h, pad_w, dil_h, dil_w, KW;
+    int P, M, K;                        // P = OH*OW
+    int ktb, cch;                       // k-tiles of the launched tile: K / bk in all, Cin / bk per filter tap
+    int ksplit, groups, n_first, MT, NT;
+    int tiles, total;                   // MT * NT; tiles * groups * ksplit = the problem's workgroups
+    FastDiv d_tiles, d_ksplit, d_MT, d_P, d_OW, d_KW, d_cch;
+    int vec_store, res_cstride, res_coff, KH, OH;
+};
+static_assert(sizeof(ConvPro) == 320, "five 64-byte lines");
+
+struct ConvK : ConvPro {
+    int y_cstride, y_coff, y_nchw;
+    int act, act2, act_split;
+    int combine;                        // split-K: 1 = last-arriver combine inside the launch, 0 = second launch
+    int KT, cchunks;                    // k-tiles of 32 (v1 and the lab families)
+    int pr;                             // weight-stationary tiles: pixel ranges per (group, 32-channel block)
     const float *zero;                  // PF = 6: 16 zero bytes, the source of padding taps for the activation DMA
     int x_split, y_split;               // the input map arrives / the result leaves in the split-fp16 layout (usot_conv_desc)
     int *ovf;                           // split-fp16 tiles: sticky "a finished sum was not finite" word (usot_conv_desc.ovf) or nullptr
-    const int *n_dyn;                   // v3 tiles: nullptr, or a device word with a run-time image count (usot_conv_desc.n_dyn): images
-    int n_first;                        // [0, clamp(*n_dyn - n_first, 0, N)) of this problem are live, the rest is neither read nor written
 };
 
 // Up to four convolutions of DIFFERENT geometry in one launch (same tile shape): the shortcut
 // conv beside conv1 of a bottleneck, the three dilated encoders of one input, the two
 // prediction heads.  At batch 1 each of these alone leaves most of the chip idle and pays a
 // full launch; side by side they share one.  Workgroup ranges are [start[i], start[i+1]).
+// n and start[] stand in front: the first scalar fetch of a kernel, which selects the problem.
 struct ConvBatch {
-    ConvK p[4];
     int n;
     int start[5];
+    int pad_[2];
+    ConvK p[4];
 };
+constexpr int kBatchHead = 64;          // bytes in front of p[0]
+static_assert(sizeof(ConvBatch) == kBatchHead + 4 * sizeof(ConvK) && sizeof(ConvK) % 64 == 0, "problem blocks on 64-byte lines");
+
+// The prologue fetch.  ConvBatch is the FIRST kernel argument of every conv kernel, so it stands at offset 0 of the kernel-argument
+// segment; reading it through the segment pointer (constant address space, uniform address) gives wide scalar loads that the
+// compiler can neither split nor sink to the fields' uses.  Two dependent rounds for a single-problem launch, three for a batch:
+//   1. n, start[] AND problem 0's block, issued together, one wait;
+//   2. only where the workgroup belongs to problem 1-3: that problem's block;
+//   3. the caller's *n_dyn.
+// The empty asm carries the values through SGPRs: behind it they are registers, not re-loadable kernel arguments.
+typedef uint32_t u32x16_t __attribute__((ext_vector_type(16)));
+typedef uint32_t u32x8_t __attribute__((ext_vector_type(8)));
+struct ConvProBits { u32x16_t v[5]; };
+static_assert(sizeof(ConvProBits) == sizeof(ConvPro), "bit image of the prologue block");
+#define USOT_KARG __attribute__((address_space(4)))
+__device__ __forceinline__ ConvPro conv_pro_fetch(int &pi, int &bid0)
+{
+    const USOT_KARG char *ka = (const USOT_KARG char *)__builtin_amdgcn_kernarg_segment_ptr();
+    u32x8_t hd = *(const USOT_KARG u32x8_t *)ka;
+    const USOT_KARG u32x16_t *b0 = (const USOT_KARG u32x16_t *)(ka + kBatchHead);
+    u32x16_t v0 = b0[0], v1 = b0[1], v2 = b0[2], v3 = b0[3], v4 = b0[4];
+    asm volatile("" : "+s"(hd), "+s"(v0), "+s"(v1), "+s"(v2), "+s"(v3), "+s"(v4));
+    const int n = (int)hd[0];
+    pi = 0;
+#pragma unroll
+    for (int q = 1; q < 4; ++q)
+        if (q < n && (int)blockIdx.x >= (int)hd[1 + q]) pi = q;
+    bid0 = (int)blockIdx.x - (pi == 0 ? (int)hd[1] : pi == 1 ? (int)hd[2] : pi == 2 ? (int)hd[3] : (int)hd[4]);
+    if (pi != 0) {
+        const USOT_KARG u32x16_t *bp = (const USOT_KARG u32x16_t *)(ka + kBatchHead + (size_t)pi * sizeof(ConvK));
+        v0 = bp[0]; v1 = bp[1]; v2 = bp[2]; v3 = bp[3]; v4 = bp[4];
+        asm volatile("" : "+s"(v0), "+s"(v1), "+s"(v2), "+s"(v3), "+s"(v4));
+    }
+    const ConvProBits bits = {{v0, v1, v2, v3, v4}};
+    ConvPro q = __builtin_bit_cast(ConvPro, bits);
+    // pointers that come out of a bit image are generic to the compiler (flat_load: counted on lgkmcnt too, which would tie the
+    // producers' loads to the LDS waits); kernel arguments point to global memory, and through these casts it knows again
+#define USOT_GLOBAL_PTR(f) q.f = (decltype(q.f))(__attribute__((address_space(1))) void *)(uintptr_t)q.f
+    USOT_GLOBAL_PTR(x); USOT_GLOBAL_PTR(w); USOT_GLOBAL_PTR(bias); USOT_GLOBAL_PTR(res);
+    USOT_GLOBAL_PTR(y); USOT_GLOBAL_PTR(ws); USOT_GLOBAL_PTR(n_dyn); USOT_GLOBAL_PTR(wscale);
+#undef USOT_GLOBAL_PTR
+    return q;
+}
+__device__ __forceinline__ int fd_div(int n, FastDiv f) { return (int)fastdiv_div((uint32_t)n, f); }
 
 __device__ __forceinline__ float apply_act(float v, int a)
 {

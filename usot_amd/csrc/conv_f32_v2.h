@@ -27,12 +27,11 @@ struct V2Geom {
 template <int BM, int BN, int WM, int WN, int BK, int KSW = 1>
 __global__ __launch_bounds__((V2Geom<BM, BN, BK, KSW>::threads)) void conv_igemm_f32_v2(const ConvBatch bt)
 {
-    int pi = 0;
-#pragma unroll
-    for (int q = 1; q < 4; ++q)
-        if (q < bt.n && (int)blockIdx.x >= bt.start[q]) pi = q;
+    // the prologue block of this workgroup's problem in SGPRs (conv_f32_common.h: conv_pro_fetch); `p` stays the way to the fields that
+    // are read behind the k-loop only
+    int pi, bid0;
+    const ConvPro q = conv_pro_fetch(pi, bid0);
     const ConvK &p = bt.p[pi];
-    const int bid0 = (int)blockIdx.x - bt.start[pi];
     static_assert(WM * WN == 4, "4 wavefronts per workgroup");
     static_assert(BK == 32 || BK == 64, "k-tile of 32 or 64");
     constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
@@ -53,19 +52,20 @@ __global__ __launch_bounds__((V2Geom<BM, BN, BK, KSW>::threads)) void conv_igemm
     float *smem = smem_all + grp * 3 * STAGE;
 
     const int tid = threadIdx.x & 255;
-    const int tiles = p.MT * p.NT;
-    const int total = tiles * p.groups * p.ksplit;
-    const int b = xcd_remap(bid0, total);
-    const int z = b / tiles, t0 = b - z * tiles;
-    const int g = z / p.ksplit, ks = z - g * p.ksplit;
-    const int bn0 = (t0 / p.MT) * BN, bm0 = (t0 % p.MT) * BM;
-    const int KT = p.K / BK;                    // k-tiles of this instantiation
-    const int cch = p.Cin / BK;
-    const int kt0 = (int)((long)KT * ks / p.ksplit);
-    const int kt1 = (int)((long)KT * (ks + 1) / p.ksplit);
+    // index prologue: every divisor is a constant of the problem, divided by with its host-made multiplier and shift (fastdiv.h)
+    const int tiles = q.tiles;
+    const int b = xcd_remap(bid0, q.total);
+    const int z = fd_div(b, q.d_tiles), t0 = b - z * tiles;
+    const int g = fd_div(z, q.d_ksplit), ks = z - g * q.ksplit;
+    const int tn0 = fd_div(t0, q.d_MT);
+    const int bn0 = tn0 * BN, bm0 = (t0 - tn0 * q.MT) * BM;
+    const int KT = q.ktb;                       // k-tiles of this instantiation
+    const int cch = q.cch;
+    const int kt0 = fd_div(KT * ks, q.d_ksplit);              // (KT * ksplit < 2^31: the launcher checks)
+    const int kt1 = fd_div(KT * (ks + 1), q.d_ksplit);
 
-    const float *__restrict__ xg = p.x + (long)g * p.x_gs;
-    const float *__restrict__ wg = p.w + (long)g * p.w_gs;
+    const float *__restrict__ xg = q.x + (long)g * q.x_gs;
+    const float *__restrict__ wg = q.w + (long)g * q.w_gs;
 
     const int lr = tid / CPR, kc = tid % CPR;
     int x_ih0[XI], x_iw0[XI];
@@ -75,13 +75,13 @@ __global__ __launch_bounds__((V2Geom<BM, BN, BK, KSW>::threads)) void conv_igemm
     for (int i = 0; i < XI; ++i) {
         const int row = lr + RPP * i;
         const int m = bm0 + row;
-        x_ok[i] = (row < BM) && (m < p.M);
+        x_ok[i] = (row < BM) && (m < q.M);
         const int mm = x_ok[i] ? m : 0;
-        const int n = mm / p.P, pix = mm - n * p.P;
-        const int oh = pix / p.OW, ow = pix - oh * p.OW;
-        x_ih0[i] = oh * p.stride - p.pad_h;
-        x_iw0[i] = ow * p.stride - p.pad_w;
-        x_nb[i] = (long)n * p.H * p.W * p.Cin + kc * 4;
+        const int n = fd_div(mm, q.d_P), pix = mm - n * q.P;
+        const int oh = fd_div(pix, q.d_OW), ow = pix - oh * q.OW;
+        x_ih0[i] = oh * q.stride - q.pad_h;
+        x_iw0[i] = ow * q.stride - q.pad_w;
+        x_nb[i] = (long)n * q.H * q.W * q.Cin + kc * 4;
     }
     long w_off[WI];
     bool w_ok[WI];
@@ -89,8 +89,8 @@ __global__ __launch_bounds__((V2Geom<BM, BN, BK, KSW>::threads)) void conv_igemm
     for (int i = 0; i < WI; ++i) {
         const int row = lr + RPP * i;
         const int co = bn0 + row;
-        w_ok[i] = (row < BN) && (co < p.Cout);
-        w_off[i] = (long)(w_ok[i] ? co : 0) * p.K + kc * 4;
+        w_ok[i] = (row < BN) && (co < q.Cout);
+        w_off[i] = (long)(w_ok[i] ? co : 0) * q.K + kc * 4;
     }
 
     // Loader state is incremental: a row's source pointer is recomputed only when the filter
@@ -100,15 +100,15 @@ __global__ __launch_bounds__((V2Geom<BM, BN, BK, KSW>::threads)) void conv_igemm
     const float *xp[XI];
     bool xin[XI];
     const float *wp[WI];
-    int cur_tap = (kt0 + grp) / cch, cur_cc = (kt0 + grp) - cur_tap * cch;
+    int cur_tap = fd_div(kt0 + grp, q.d_cch), cur_cc = (kt0 + grp) - cur_tap * cch;
     auto set_tap = [&](int tap) {
-        const int kh = tap / p.KW, kw = tap - kh * p.KW;
-        const int dh = kh * p.dil_h, dw = kw * p.dil_w;
+        const int kh = fd_div(tap, q.d_KW), kw = tap - kh * q.KW;
+        const int dh = kh * q.dil_h, dw = kw * q.dil_w;
 #pragma unroll
         for (int i = 0; i < XI; ++i) {
             const int ih = x_ih0[i] + dh, iw = x_iw0[i] + dw;
-            xin[i] = x_ok[i] && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-            xp[i] = xg + x_nb[i] + ((long)ih * p.W + iw) * p.Cin;
+            xin[i] = x_ok[i] && (unsigned)ih < (unsigned)q.H && (unsigned)iw < (unsigned)q.W;
+            xp[i] = xg + x_nb[i] + ((long)ih * q.W + iw) * q.Cin;
         }
     };
     set_tap(cur_tap);

@@ -65,14 +65,20 @@ template <int BM, int BN, int WM, int WN, int BK, int D = 1, int NPW = 4, int PF
 __global__ __launch_bounds__((V3Geom<BM, BN, WM, WN, BK, D, NPW, PF>::threads)) void conv_igemm_f32_v3(const ConvBatch bt)
 {
     using Geo = V3Geom<BM, BN, WM, WN, BK, D, NPW, PF>;
-    int pi = 0;
-#pragma unroll
-    for (int q = 1; q < 4; ++q)
-        if (q < bt.n && (int)blockIdx.x >= bt.start[q]) pi = q;
+#ifdef USOT_TRACE
+    const unsigned tr_entry = (unsigned)__builtin_readcyclecounter();
+#endif
+    // the prologue block of this workgroup's problem in SGPRs (conv_f32_common.h: conv_pro_fetch); `p` stays the way to the fields that
+    // are read behind the k-loop only
+    int pi, bid0;
+    const ConvPro q = conv_pro_fetch(pi, bid0);
     const ConvK &p = bt.p[pi];
     // run-time image count (usot_conv_desc.n_dyn): the load is issued first and used behind the index prologue
-    const int dyn_n = p.n_dyn ? *p.n_dyn : 0;
-    const int bid0 = (int)blockIdx.x - bt.start[pi];
+    // (a scalar fetch through the constant address space: the third and last dependent scalar round of the prologue.  The scalar cache
+    // is refreshed at a dispatch boundary only, so the word must be complete before this launch starts: written by an EARLIER kernel
+    // or copy of the stream / graph chain, never by anything that may run concurrently with this launch - this kernel itself, a
+    // parallel graph branch, another stream or the host)
+    const int dyn_n = q.n_dyn ? *(const USOT_KARG int *)(uintptr_t)q.n_dyn : 0;
     // WM x WN consumer wavefronts: 4 (one per SIMD) or 8 (two per SIMD, round 5: the same tile in smaller wave tiles, nothing to
     // exchange).  Probe (scripts/probes/coissue_probe.hip, inline-asm reads, independent accumulators): a SIBLING wave's VALU / SALU /
     // LDS / VMEM instructions do not delay a wave's back-to-back MFMAs at all (32.0 cycles each); the wave's OWN ds_read_b128, issued
@@ -119,21 +125,22 @@ __global__ __launch_bounds__((V3Geom<BM, BN, WM, WN, BK, D, NPW, PF>::threads)) 
     const bool producer = threadIdx.x >= CT;
     const int tid = producer ? (int)threadIdx.x - CT : (int)threadIdx.x;
     constexpr int NPTL = Geo::NPT;                // producer threads actually launched (none when the activations come by DMA)
-    const int tiles = p.MT * p.NT;
-    const int total = tiles * p.groups * p.ksplit;
-    const int b = xcd_remap(bid0, total);
-    const int z = b / tiles, t0 = b - z * tiles;
-    const int g = z / p.ksplit, ks = z - g * p.ksplit;
-    const int bn0 = (t0 / p.MT) * BN, bm0 = (t0 % p.MT) * BM;
-    const int KT = p.K / BK;
-    const int cch = p.Cin / BK;
-    const int kt0 = (int)((long)KT * ks / p.ksplit);
-    const int kt1 = (int)((long)KT * (ks + 1) / p.ksplit);
+    // index prologue: every divisor is a constant of the problem, divided by with its host-made multiplier and shift (fastdiv.h)
+    const int tiles = q.tiles;
+    const int b = xcd_remap(bid0, q.total);
+    const int z = fd_div(b, q.d_tiles), t0 = b - z * tiles;
+    const int g = fd_div(z, q.d_ksplit), ks = z - g * q.ksplit;
+    const int tn0 = fd_div(t0, q.d_MT);
+    const int bn0 = tn0 * BN, bm0 = (t0 - tn0 * q.MT) * BM;
+    const int KT = q.ktb;
+    const int cch = q.cch;
+    const int kt0 = fd_div(KT * ks, q.d_ksplit);              // (KT * ksplit < 2^31: the launcher checks)
+    const int kt1 = fd_div(KT * (ks + 1), q.d_ksplit);
     const int nt = kt1 - kt0;
     // ML = the rows this launch computes: M, or with n_dyn the rows of the live images.  A workgroup whose tile lies past them leaves
     // here - before LDS, the split-K slabs, the tickets or the ovf word are touched (every k-slice of a tile takes the same decision, so
     // the tickets stay zero); a tile that straddles ML treats the rows past it as rows past M: not loaded (zeros), not stored
-    const int ML = p.n_dyn ? min(max(dyn_n - p.n_first, 0), p.N) * p.P : p.M;
+    const int ML = q.n_dyn ? min(max(dyn_n - q.n_first, 0), q.N) * q.P : q.M;
     if (bm0 >= ML) return;
 
     if constexpr (WDMA) {
@@ -147,7 +154,7 @@ __global__ __launch_bounds__((V3Geom<BM, BN, WM, WN, BK, D, NPW, PF>::threads)) 
             constexpr int NCHX = BM * 17;                      // the activation stage likewise (PF = 6)
             constexpr int NPX = XDMA ? (NCHX + 63) / 64 : 0;
             constexpr int MAXPX = XDMA ? (NPX + NDW - 1) / NDW : 1;
-            const float *__restrict__ wg = p.w + (long)g * p.w_gs + (long)kt0 * BK;
+            const float *__restrict__ wg = q.w + (long)g * q.w_gs + (long)kt0 * BK;
             const float *src[MAXP];
             bool live[MAXP];
             int mine = 0;                                      // pieces this wave moves per k-tile (wave-uniform)
@@ -256,8 +263,8 @@ __global__ __launch_bounds__((V3Geom<BM, BN, WM, WN, BK, D, NPW, PF>::threads)) 
     }
 
     if (producer) {
-        const float *__restrict__ xg = p.x + (long)g * p.x_gs;
-        const float *__restrict__ wg = p.w + (long)g * p.w_gs;
+        const float *__restrict__ xg = q.x + (long)g * q.x_gs;
+        const float *__restrict__ wg = q.w + (long)g * q.w_gs;
         const int lr = tid / CPR, kc = tid % CPR;
         int x_ih0[XI], x_iw0[XI];
         long x_nb[XI];
@@ -268,32 +275,32 @@ __global__ __launch_bounds__((V3Geom<BM, BN, WM, WN, BK, D, NPW, PF>::threads)) 
             const int m = bm0 + row;
             x_ok[i] = (row < BM) && (m < ML);
             const int mm = x_ok[i] ? m : 0;
-            const int n = mm / p.P, pix = mm - n * p.P;
-            const int oh = pix / p.OW, ow = pix - oh * p.OW;
-            x_ih0[i] = oh * p.stride - p.pad_h;
-            x_iw0[i] = ow * p.stride - p.pad_w;
-            x_nb[i] = (long)n * p.H * p.W * p.Cin + kc * 4;
+            const int n = fd_div(mm, q.d_P), pix = mm - n * q.P;
+            const int oh = fd_div(pix, q.d_OW), ow = pix - oh * q.OW;
+            x_ih0[i] = oh * q.stride - q.pad_h;
+            x_iw0[i] = ow * q.stride - q.pad_w;
+            x_nb[i] = (long)n * q.H * q.W * q.Cin + kc * 4;
         }
         const float *wp[WI];
 #pragma unroll
         for (int i = 0; i < WI; ++i) {
             const int row = lr + RPP * i;
             const int co = bn0 + row;
-            wp[i] = wg + (long)((row < BN && co < p.Cout) ? co : 0) * p.K + kc * 4 + (long)kt0 * BK;
+            wp[i] = wg + (long)((row < BN && co < q.Cout) ? co : 0) * q.K + kc * 4 + (long)kt0 * BK;
         }
         f32x4 xr[D][XI], wr[D][WI];
         bool xz[D][XI];
         const float *xp[XI];
         bool xin[XI];
-        int cur_tap = kt0 / cch, cur_cc = kt0 - cur_tap * cch;
+        int cur_tap = fd_div(kt0, q.d_cch), cur_cc = kt0 - cur_tap * cch;
         auto set_tap = [&](int tap) {
-            const int kh = tap / p.KW, kw = tap - kh * p.KW;
-            const int dh = kh * p.dil_h, dw = kw * p.dil_w;
+            const int kh = fd_div(tap, q.d_KW), kw = tap - kh * q.KW;
+            const int dh = kh * q.dil_h, dw = kw * q.dil_w;
 #pragma unroll
             for (int i = 0; i < XI; ++i) {
                 const int ih = x_ih0[i] + dh, iw = x_iw0[i] + dw;
-                xin[i] = x_ok[i] && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
-                xp[i] = xg + x_nb[i] + ((long)ih * p.W + iw) * p.Cin;
+                xin[i] = x_ok[i] && (unsigned)ih < (unsigned)q.H && (unsigned)iw < (unsigned)q.W;
+                xp[i] = xg + x_nb[i] + ((long)ih * q.W + iw) * q.Cin;
             }
         };
         set_tap(cur_tap);
@@ -378,12 +385,20 @@ __global__ __launch_bounds__((V3Geom<BM, BN, WM, WN, BK, D, NPW, PF>::threads)) 
         // map from the other XCDs' write-backs), a round trip is 2-3 k-steps long.
         int lt = 0;                                   // next tile to fetch
         auto load_next = [&](auto dc) { load_tile(dc, lt + 1 < nt); ++lt; };
+#ifdef USOT_TRACE
+        unsigned tr_load = 0, tr_barrier = 0;
+#define USOT_START(v) v = (unsigned)__builtin_readcyclecounter()
+#else
+#define USOT_START(v)
+#endif
         if constexpr (D == 1) {
             load_next(I0{}); store_tile(I0{}, 0);
+            USOT_START(tr_load);
             load_next(I0{}); if (nt > 1) store_tile(I0{}, 1);
         } else {
             load_next(I0{});
             load_next(I1{});
+            USOT_START(tr_load);                      // the x and w loads of k-tiles 0 and 1 are issued
             store_tile(I0{}, 0);
             if (nt > 1) store_tile(I1{}, 1);
         }
@@ -395,8 +410,12 @@ __global__ __launch_bounds__((V3Geom<BM, BN, WM, WN, BK, D, NPW, PF>::threads)) 
         __syncthreads();
         int st2 = 2;                                  // stage that receives tile t+2
 #ifdef USOT_TRACE   // scripts/trace_kstep.py: s_memtime stamps of one producer wave into the (unused) split-K workspace
+        USOT_START(tr_barrier);
         unsigned *trc = (p.ksplit == 1 && p.ws && bid0 == 0 && tid == 0) ? (unsigned *)p.ws : nullptr;
 #define USOT_STAMP(slot, t) if (trc && (t) < 64) trc[(t) * 8 + (slot)] = (unsigned)__builtin_readcyclecounter()
+        // start-up stamps, row 60 of the table (layer3's 3x3 has 36 k-tiles): kernel entry, first four loads issued, first barrier passed;
+        // the first k-step begins at row 0's slot 4
+        if (trc) { trc[60 * 8 + 0] = tr_entry; trc[60 * 8 + 1] = tr_load; trc[60 * 8 + 2] = tr_barrier; }
 #else
 #define USOT_STAMP(slot, t)
 #endif
@@ -511,23 +530,23 @@ __global__ __launch_bounds__((V3Geom<BM, BN, WM, WN, BK, D, NPW, PF>::threads)) 
     // bias and residual of this lane's outputs are fetched NOW, while the producers bring the first k-tiles:
     // loaded in the epilogue they add a dependent L2/HBM round trip to the tail of every layer, when no
     // other work is left to hide it.  (vectorised NHWC stores without split-K only.)
-    const bool pre = p.vec_store && p.ksplit == 1;
+    const bool pre = q.vec_store && q.ksplit == 1;
     f32x4 pb[TN], pr[TN][TM];
     f32x4 psc[H16 ? TN : 1];                      // split-fp16: this lane's four output-channel scales per block, fetched up front too
 #pragma unroll
     for (int i = 0; i < TN; ++i) {
         const int co = bn0 + (wn * TN + i) * 16 + quad * 4;
-        const bool cok = pre && co + 3 < p.Cout;
-        pb[i] = (cok && p.bias) ? *(const f32x4 *)(p.bias + (long)g * p.b_gs + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+        const bool cok = pre && co + 3 < q.Cout;
+        pb[i] = (cok && q.bias) ? *(const f32x4 *)(q.bias + (long)g * q.b_gs + co) : f32x4{0.f, 0.f, 0.f, 0.f};
         if constexpr (H16) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) psc[i][e] = co + e < p.Cout ? p.wscale[(long)g * p.b_gs + co + e] : 0.f;      // (the bias' group stride: rows of the bank per group)
+            for (int e = 0; e < 4; ++e) psc[i][e] = co + e < q.Cout ? q.wscale[(long)g * q.b_gs + co + e] : 0.f;      // (the bias' group stride: rows of the bank per group)
         }
 #pragma unroll
         for (int j = 0; j < TM; ++j) {
             const int m = bm0 + (wm * TM + j) * 16 + l15;
-            pr[i][j] = (cok && p.res && m < ML)
-                           ? *(const f32x4 *)(p.res + (long)g * p.r_gs + (long)m * p.res_cstride + p.res_coff + co)
+            pr[i][j] = (cok && q.res && m < ML)
+                           ? *(const f32x4 *)(q.res + (long)g * q.r_gs + (long)m * q.res_cstride + q.res_coff + co)
                            : f32x4{0.f, 0.f, 0.f, 0.f};
         }
     }
@@ -637,6 +656,7 @@ __global__ __launch_bounds__((V3Geom<BM, BN, WM, WN, BK, D, NPW, PF>::threads)) 
         USOT_STAMP(2, t);
     }
 #undef USOT_STAMP
+#undef USOT_START
     flush();
 #pragma unroll
     for (int i = 0; i < TN; ++i)

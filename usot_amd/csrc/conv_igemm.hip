@@ -368,6 +368,9 @@ int fill_params(const usot_conv_desc *d, ConvK &p)
     p.ksplit = ksplit;
     if (d->defer && ksplit < 2) return USOT_EINVAL;
     p.combine = d->defer ? 0 : 1;            // deferred reduction: the slabs ARE the result (plain stores, no tickets)
+    // rows, taps and reduction length are dividends of the kernels' multiply-and-shift divisions (fastdiv.h): exact below 2^31 only
+    if ((int64_t)d->N * d->OH * d->OW > (int64_t)FASTDIV_MAX_DIVIDEND || (int64_t)d->KH * d->KW * d->Cin > (int64_t)FASTDIV_MAX_DIVIDEND)
+        return USOT_EINVAL;
     p.P = d->OH * d->OW;
     p.M = d->N * p.P;
     p.K = d->KH * d->KW * d->Cin;
@@ -477,8 +480,24 @@ extern "C" int usot_conv2d_batch_f32(void *stream, const usot_conv_desc *d, int 
         if (tc.wfrag == 1 && p.groups > 1 && (p.w_gs % ((long)16 * p.K))) return USOT_EINVAL;
         p.MT = (p.M + tc.bm - 1) / tc.bm;
         p.NT = (d[i].Cout + tc.bn - 1) / tc.bn;
+        // the rest of the prologue block (conv_f32_common.h: ConvPro): the tile's k-tile counts, the workgroup counts and the division
+        // constants of every divisor the index prologue and the tap walk divide by.  Dividends: workgroup index < total, tile index
+        // < tiles, row < M, pixel < P, k-tile bound <= ktb * ksplit, k-tile < ktb, tap < KH * KW - all kept below 2^31 here.
+        const int64_t total = (int64_t)p.MT * p.NT * p.groups * p.ksplit;
+        p.ktb = p.K / tc.bk;
+        p.cch = d[i].Cin / tc.bk;
+        if (total > (int64_t)FASTDIV_MAX_DIVIDEND || (int64_t)p.ktb * p.ksplit > (int64_t)FASTDIV_MAX_DIVIDEND) return USOT_EINVAL;
+        p.tiles = p.MT * p.NT;
+        p.total = (int)total;
+        p.d_tiles = fastdiv_make((uint32_t)p.tiles);
+        p.d_ksplit = fastdiv_make((uint32_t)p.ksplit);
+        p.d_MT = fastdiv_make((uint32_t)p.MT);
+        p.d_P = fastdiv_make((uint32_t)p.P);
+        p.d_OW = fastdiv_make((uint32_t)p.OW);
+        p.d_KW = fastdiv_make((uint32_t)p.KW);
+        p.d_cch = fastdiv_make((uint32_t)p.cch);
         bt.start[i] = (int)blocks;
-        blocks += (long)p.MT * p.NT * p.groups * p.ksplit;
+        blocks += total;
     }
     for (int i = n; i < 5; ++i) bt.start[i] = (int)blocks;
     if (blocks <= 0 || blocks > 0x7fffffffL) return USOT_EINVAL;
