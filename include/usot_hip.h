@@ -580,11 +580,25 @@ typedef struct usot_groupdw_desc {
     int32_t x_cs[3], x_co[3], z_cs[3], z_co[3];
     float wsm[3];
     int32_t S, x_rep, OH, OW, C;
-    int32_t cols_per_thread;     /* kernel variant: 0 auto (strips for a frame; from 64 samples up the LDS-DMA
-                                  * kernel for 25- and 27-wide responses, else ring);
-                                  * 1: 5x1 strips; 50: 5x5 patches; 2: column threads;
-                                  * 3: LDS row streaming; 4: ring (taps in LDS, rows streamed once);
-                                  * 6: LDS-DMA (loader waves feed row-sets to LDS, 7-column strip waves) */
+    int32_t cols_per_thread;     /* kernel variant, read from d[0]; every variant computes the same sums (tests/test_gpu_groupdw_sweep.py):
+                                  *  0  auto: below 64 samples 1; from 64 samples up 7 for 25- and 27-wide responses when every
+                                  *     segment has x_rep 1, 6 when one shares its maps, 4 for OW 21 .. 30, else 1
+                                  *  1  5x1 strips (what a single frame runs; the only variant that takes a run-time count)
+                                  *  5 / 50 / 52  5x5 patches at 4 / 1 / 2 waves per SIMD (register budgets)
+                                  *  2  column threads, OH <= 32
+                                  *  3  LDS row streaming, OW 21 .. 30; 16-byte loads of the search rows: every x[b] 16-byte
+                                  *     aligned, x_cs and x_co multiples of 4
+                                  *  4  ring (taps in LDS, rows streamed once), OW 21 .. 30
+                                  *  6 / 7  LDS-DMA (loader waves feed row-sets to LDS, 7-column strip waves) with the default /
+                                  *     the non-temporal load policy, OW 25 or 27; x aligned as for 3
+                                  *  8 / 9  the persistent form of 6 / 7 (the resident workgroups walk the (sample, channel group)
+                                  *     units), OW 25 or 27; x AND z aligned as for 3 (the taps are DMA pieces too)
+                                  * 1, 2, 4, 5, 50, 52 load by dwords: any x_cs / x_co / z_cs / z_co; 3, 6, 7 any z_cs / z_co.
+                                  * OH is free except for 2.  6, 7, 8, 9 give the same bits.
+                                  * USOT_EINVAL, nothing launched and no output written: nseg outside 1 .. 3, OH or OW < 1, C not a
+                                  * positive multiple of 64, S < 1, x_rep < 1, a NULL x / z / out, hk / wk other than 5x5, 3x5, 5x3,
+                                  * a segment whose OH / OW / C differs from d[0]'s, any other code, a geometry or an alignment the
+                                  * variant does not take */
 } usot_groupdw_desc;
 int usot_groupdw_f32(void *stream, const usot_groupdw_desc *d);
 /* the cols_per_thread code the launcher resolves 0 (auto) to for this many samples (benchmarks name

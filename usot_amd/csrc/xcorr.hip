@@ -719,9 +719,14 @@ __global__ __launch_bounds__(512) void groupdw_dma_kernel(const GdwK p)
             } else {
                 uint16_t *orow = (uint16_t *)g.out + (o - g.out) + (long)(r - 4) * p.OW * p.C;
 #pragma unroll
-                for (int j = 0; j < 7; ++j)
+                for (int j = 0; j < 7; ++j) {
+                    // the fp32 sum as a value of its own: left to itself hipcc folds the row's last FMA and the fp16 conversion into one
+                    // v_fma_mixlo_f16, which rounds the exact sum ONCE, to fp16 - not the rounding of what the fp32 launch stores
+                    float a = A[DONE][j];
+                    asm volatile("" : "+v"(a));
                     if (j < nvalid)
-                        orow[(long)j * p.C] = OT == 1 ? __builtin_bit_cast(uint16_t, (_Float16)A[DONE][j]) : __builtin_bit_cast(uint16_t, (__bf16)A[DONE][j]);
+                        orow[(long)j * p.C] = OT == 1 ? __builtin_bit_cast(uint16_t, (_Float16)a) : __builtin_bit_cast(uint16_t, (__bf16)a);
+                }
             }
         }
 #pragma unroll
@@ -1230,6 +1235,9 @@ static int groupdw_multi_impl(void *stream, const usot_groupdw_desc *d, int nseg
     if (mode == 3) {            // streaming: one workgroup per (sample, 64-channel group)
         const int nstrip = (p.OW + 4) / 5;
         if (nstrip != 5 && nstrip != 6) return USOT_EINVAL;
+        for (int sidx = 0; sidx < nseg; ++sidx)
+            for (int b = 0; b < 3; ++b)        // 16-byte vector loads of search rows
+                if (((uintptr_t)p.seg[sidx].x[b] & 15) || (p.seg[sidx].x_cs[b] & 3) || (p.seg[sidx].x_co[b] & 3)) return USOT_EINVAL;
         p.total = total;
         p.nty = p.ntx = 1;
         const long nb = p.C == 256 ? 8L * ((total + 1) / 2) : (long)(p.C / 64) * total;
