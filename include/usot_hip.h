@@ -178,6 +178,10 @@ int usot_conv_bf16_tile_count(void);
 int usot_stem_pool_lp(void *stream, const float *x, const void *wfrag, const float *bias, void *y,
                       int N, int H, int W, int OH, int OW, int PH, int PW, int dtype,
                       float mu0, float mu1, float mu2);
+/* host only: the number of 4x8 pooled tiles a workgroup of usot_stem_pool_lp walks along x for a launch of this size
+ * (4, 2 or 1: the longest strip that still leaves six workgroups per compute unit of a 256-CU device); 0 for N, PH or
+ * PW < 1.  The launcher takes its strip from this function. */
+int usot_stem_pool_lp_strip(int N, int PH, int PW);
 int usot_cvt_f32_to_bf16(void *stream, const float *src, void *dst, int64_t n);
 int usot_maxpool3x3s2_bf16(void *stream, const void *x, void *y, int N, int H, int W, int C, int OH, int OW);
 
@@ -373,7 +377,7 @@ int usot_stem_conv_f32(void *stream, const float *x, const float *w, const float
                        float *y, int N, int H, int W, int OH, int OW);
 /* the same on x - mu[ci] (exact for this pad-0 conv; `bias` must then carry + sum_k w[k][co] * mu[ci(k)], folded in
  * float64 by the caller): raw crops sit around ~100, and the 147-tap float32 chain of every output otherwise rides on
- * 100 * sum(w).  mu = 0 is usot_stem_conv_f32. */
+ * 100 * sum(w).  mu = 0 is usot_stem_conv_f32.  N <= 65535 (one grid plane per image), as in the fused forms. */
 int usot_stem_conv_mu_f32(void *stream, const float *x, const float *w, const float *bias,
                           float *y, int N, int H, int W, int OH, int OW, float mu0, float mu1, float mu2);
 

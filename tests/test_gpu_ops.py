@@ -1140,7 +1140,8 @@ def test_stem_pool_lp(size, n, dtype, wdtype):
     """Fused MFMA stem + max-pool vs torch on the SAME rounded operands (filters rounded to the
     fragment type; crop rounded to fp16, or to hi + lo bf16 pairs; fp32 accumulate): differences are
     accumulation order + one final rounding, i.e. at most 1 ulp of the storage type.  Third mode: fp16 fragments and crop,
-    bf16 output (the stem of the bf16 backbone).  (255, 9): enough tiles for strips of 2 per workgroup."""
+    bf16 output (the stem of the bf16 backbone).  Every case here, (255, 9) with its 8 x 16 x 9 tiles included, stays below the 1536
+    workgroups a strip of 2 needs and walks one tile per workgroup; strips of 2 and 4 are run by test_gpu_stem_sweep.py."""
     from usot_amd.engine import pack_stem_lp
     g = torch.Generator().manual_seed(size + n)
     x = (torch.rand(n, 3, size, size, generator=g) * 2 - 1) * 3

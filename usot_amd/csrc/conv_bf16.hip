@@ -1171,6 +1171,16 @@ extern "C" int usot_maxpool3x3s2_bf16(void *stream, const void *x, void *y, int 
  * (BN folded) in the storage type, pre-swizzled as MFMA A fragments [4][6][64][8] (see
  * usot_amd/engine.py: pack_stem_lp); bias fp32[64] INCLUDING sum_k w[co][k] * mu[ci(k)] (the kernel
  * convolves x - mu); y NHWC [N][PH][PW][64] in the storage type. */
+extern "C" int usot_stem_pool_lp_strip(int N, int PH, int PW)
+{
+    if (N < 1 || PH < 1 || PW < 1) return 0;
+    const int tiles_x = usot_cdiv(PW, SP_Q), tiles_y = usot_cdiv(PH, SP_P);
+    // strip length: the longest of 4, 2, 1 that still leaves >= 6 workgroups per CU (three are resident)
+    int strip = 4;                                              // (1 / 2 / 4 / 8 measured at batch 64: 106 / 103 / 98 / 99 us)
+    while (strip > 1 && (long)usot_cdiv(tiles_x, strip) * tiles_y * N < 6 * 256) strip >>= 1;
+    return strip;
+}
+
 extern "C" int usot_stem_pool_lp(void *stream, const float *x, const void *wfrag, const float *bias, void *y,
                                  int N, int H, int W, int OH, int OW, int PH, int PW, int dtype,
                                  float mu0, float mu1, float mu2)
@@ -1180,9 +1190,7 @@ extern "C" int usot_stem_pool_lp(void *stream, const float *x, const void *wfrag
     if (PH != (OH + 2 - 3) / 2 + 1 || PW != (OW + 2 - 3) / 2 + 1) return USOT_EINVAL;
     if (((uintptr_t)wfrag % 16) || ((uintptr_t)y % 16) || ((uintptr_t)bias % 16) || N > 65535) return USOT_EINVAL;
     const int tiles_x = usot_cdiv(PW, SP_Q), tiles_y = usot_cdiv(PH, SP_P);
-    // strip length: the longest of 4, 2, 1 that still leaves >= 6 workgroups per CU (three are resident)
-    int strip = 4;                                              // (1 / 2 / 4 / 8 measured at batch 64: 106 / 103 / 98 / 99 us)
-    while (strip > 1 && (long)usot_cdiv(tiles_x, strip) * tiles_y * N < 6 * 256) strip >>= 1;
+    const int strip = usot_stem_pool_lp_strip(N, PH, PW);
     dim3 grid(usot_cdiv(tiles_x, strip), tiles_y, N);
     if (dtype == 2) hipLaunchKernelGGL((stem_pool_lp_kernel<true, false>), grid, dim3(256), 0, (hipStream_t)stream, x, (const u32x4 *)wfrag, bias, (uint16_t *)y, H, W, OH, OW, PH, PW, mu0, mu1, mu2, strip, tiles_x);
     else if (dtype) hipLaunchKernelGGL(stem_pool_lp_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, x, (const u32x4 *)wfrag, bias, (uint16_t *)y, H, W, OH, OW, PH, PW, mu0, mu1, mu2, strip, tiles_x);

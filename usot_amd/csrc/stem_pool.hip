@@ -260,7 +260,7 @@ extern "C" int usot_stem_conv_f32(void *stream, const float *x, const float *w, 
 extern "C" int usot_stem_conv_mu_f32(void *stream, const float *x, const float *w, const float *bias,
                                      float *y, int N, int H, int W, int OH, int OW, float mu0, float mu1, float mu2)
 {
-    if (!x || !w || !bias || !y || N <= 0 || H < 7 || W < 7) return USOT_EINVAL;
+    if (!x || !w || !bias || !y || N <= 0 || N > 65535 || H < 7 || W < 7) return USOT_EINVAL;
     if (OH != (H - 7) / 2 + 1 || OW != (W - 7) / 2 + 1) return USOT_EINVAL;
     if ((uintptr_t)y % 16) return USOT_EINVAL;
     if ((uintptr_t)w % 16) return USOT_EINVAL;

@@ -38,6 +38,7 @@ EXPORTS = (
     'usot_conv2d_wgrad_f32', 'usot_conv2d_dgrad_f32', 'usot_conv2d_wgrad_ws_floats', 'usot_conv2d_wgrad_psplit', 'usot_conv2d_wgrad_geometry',
     'usot_conv_pack_dgrad_f32', 'usot_conv2d_dgrad_route',
     'usot_batchnorm_fwd_f32', 'usot_batchnorm_bwd_f32', 'usot_batchnorm_ws_floats', 'usot_batchnorm_slices', 'usot_batchnorm_geometry',
+    'usot_stem_pool_lp_strip',
 )
 
 
@@ -227,6 +228,7 @@ def lib():
         L.usot_pw_single_f32_supported.argtypes = [C.c_int] * 2
         L.usot_stream_conv3x3_f32_supported.argtypes = [C.c_int] * 2
         L.usot_pw_triple_f32_supported.argtypes = [C.c_int] * 4
+        L.usot_stem_pool_lp_strip.argtypes = [C.c_int] * 3
         L.usot_plan_add_cvt_lp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int]
         L.usot_plan_add_maxpool_lp.argtypes = [C.c_void_p] + [C.c_void_p] * 2 + [C.c_int] * 7
         L.usot_plan_fork.argtypes = [C.c_void_p, C.c_int]
