@@ -724,7 +724,7 @@ __global__ __launch_bounds__(1024) void decode_kernel(
             roi_out[0] = 0.f;
             for (int e = 0; e < 4; ++e) {
                 double v = (double)(float)bx[e];
-                v = fmin(fmax(v, lo - gap), hi + gap);
+                v = v < lo - gap ? lo - gap : (v > hi + gap ? hi + gap : v);      // np.clip: a NaN stays a NaN (fmax / fmin would drop it)
                 roi_out[1 + e] = (float)((v - lo) * slope);
             }
         }

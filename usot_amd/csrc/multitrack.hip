@@ -115,7 +115,7 @@ __global__ __launch_bounds__(1024) void decode_batch_kernel(
         roi[0] = (float)b;
         for (int e = 0; e < 4; ++e) {
             double v = (double)(float)bx[e];
-            v = fmin(fmax(v, lo - gap), hi + gap);
+            v = v < lo - gap ? lo - gap : (v > hi + gap ? hi + gap : v);      // np.clip: a NaN stays a NaN (fmax / fmin would drop it)
             roi[1 + e] = (float)((v - lo) * slope);
         }
         // results first, system-scope fence, then this slot's tag (the host polls all B tags)
@@ -164,8 +164,8 @@ __global__ __launch_bounds__(256) void rows_append_gather_batch_kernel(const Row
         const int r = i / rl, e = i - r * rl;
         const int row = rows[r];
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (row == app) v = fresh[e];
-        else if (row >= 0 && row < k.bank_rows) v = bank[(long)row * rl + e];
+        // the range first: an append outside it was dropped, so a pick that equals it names no row either
+        if (row >= 0 && row < k.bank_rows) v = row == app ? fresh[e] : bank[(long)row * rl + e];
         dst[i] = v;
     }
 }
