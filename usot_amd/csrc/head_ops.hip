@@ -845,9 +845,9 @@ extern "C" int usot_prroi_pool_backward_f32(void *stream, const float *rois, con
                                             int R, int B, int C, int H, int W, int PH, int PW, float scale)
 {
     if (R < 0 || B <= 0 || C <= 0 || H <= 0 || W <= 0 || PH <= 0 || PW <= 0 || !bottom_diff) return USOT_EINVAL;
+    if (R > 0 && (!rois || !top_diff)) return USOT_EINVAL;      /* refused before the memset: a refusal writes nothing */
     if (hipMemsetAsync(bottom_diff, 0, sizeof(float) * (size_t)B * C * H * W, (hipStream_t)stream) != hipSuccess) return USOT_ELAUNCH;
     if (R == 0) return USOT_OK;
-    if (!rois || !top_diff) return USOT_EINVAL;
     PrGradK p{nullptr, rois, nullptr, top_diff, bottom_diff, R, B, C, H, W, PH, PW, scale};
     const long total = (long)R * C * PH * PW;
     const int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
