@@ -35,9 +35,11 @@ def out_hw(c):
 
 
 def route_a(c):
-    """stride 1, whole 32-channel blocks of dy, pad' = dil*(k-1) - pad >= 0"""
-    n, h, w, cin, cout, k, s, pad, dil = c
-    return s == 1 and cout % 32 == 0 and dil[0] * (k - 1) >= pad[0] and dil[1] * (k - 1) >= pad[1]
+    """stride 1, whole 32-channel blocks of dy, pad' = dil*(k-1) - pad >= 0.  Also takes the ten-field cases of
+    conv_grad_sweep_cases.py, (.., KH, KW, stride, pad, dil): rectangular filters."""
+    n, h, w, cin, cout, kh = c[:6]
+    kw, (s, pad, dil) = (kh if len(c) == 9 else c[6]), c[-3:]
+    return s == 1 and cout % 32 == 0 and dil[0] * (kh - 1) >= pad[0] and dil[1] * (kw - 1) >= pad[1]
 
 
 ROUTE_A = [c for c in RAW if route_a(c)]

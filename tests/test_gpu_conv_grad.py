@@ -48,7 +48,7 @@ def geo(c):
 def operands(c, seed=0):
     """device operands in the kernels' layouts: x NHWC, packed bank, dy NHWC"""
     (x, wt, b, dy), _ = cg.reference(c, seed)
-    return cg.nhwc(x).to(DEV), cg.pack(wt).to(DEV), cg.nhwc(dy).to(DEV)
+    return guarded.put(cg.nhwc(x), DEV), guarded.put(cg.pack(wt), DEV), guarded.put(cg.nhwc(dy), DEV)     # a NaN on both sides
 
 
 def raw_wgrad(c, xh, dyh, psplit=0, bias=True):
