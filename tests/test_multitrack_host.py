@@ -5,12 +5,14 @@ of the reference's one-video-after-another loop (scripts/test_usot.py:72-105).""
 import ctypes as C
 import os
 import re
+import threading
 
 import numpy as np
 import pytest
+import torch
 
 from usot_amd import build, hip
-from usot_amd.engine import IDLE_TSZ, SLOT_REC, STEP_HDR, SlotBook, crop_fields
+from usot_amd.engine import IDLE_TSZ, SLOT_REC, STEP_HDR, MemoryBank, SlotBook, crop_fields, wait_tags
 from usot_amd.hostutils import crop_geometry
 from usot_amd.io_utils import cxy_wh_2_rect, get_axis_aligned_bbox, poly_iou
 from usot_amd.multitrack import track_dataset
@@ -238,3 +240,61 @@ def test_track_dataset_schedules_like_the_sequential_loop(vot):
     got1 = track_dataset(None, ds, slots=1, imread=_imread, vot=vot, tracker=StubTracker(slots=1))
     for name in ds:
         _same(got1[name], want[name])
+
+
+@pytest.mark.parametrize('slots', [1, 3])
+def test_memory_bank_growth_keeps_every_slots_rows(slots):
+    """engine.MemoryBank.grow on CPU tensors: after one doubling old row r of slot b sits at b * 8 + r with its values, the new
+    rows are zero; at slots = 1 that is the single session's copy (the first `cap` rows unchanged, zeros behind them)."""
+    bank = MemoryBank(slots, 4, 'cpu')
+    tensors = [bank.feat] + bank.enc
+    for t in tensors:
+        assert t.shape[0] == slots * 4
+        for b in range(slots):
+            for r in range(4):
+                t[b * 4 + r] = float(b * 100 + r)
+    before = [t.clone() for t in tensors]
+    bank.grow()
+    assert bank.cap == 8
+    for old, t in zip(before, [bank.feat] + bank.enc):
+        assert tuple(t.shape) == (slots * 8,) + tuple(old.shape[1:]) and t.dtype == old.dtype
+        for b in range(slots):
+            assert torch.equal(t[b * 8:b * 8 + 4], old[b * 4:b * 4 + 4])
+            assert torch.equal(t[b * 8:b * 8 + 4], torch.stack([torch.full(old.shape[1:], float(b * 100 + r)) for r in range(4)]))
+            assert not t[b * 8 + 4:b * 8 + 8].any()
+        if slots == 1:
+            want = torch.zeros_like(t)
+            want[:4].copy_(old)
+            assert torch.equal(t, want)
+    ptrs, lens = bank.marshal()
+    assert list(ptrs) == [t.data_ptr() for t in [bank.feat] + bank.enc] and list(lens) == [7 * 7 * 256, 5 * 5 * 256, 3 * 5 * 256, 5 * 3 * 256]
+
+
+class _Stream(object):
+    syncs = 0
+
+    def synchronize(self):
+        self.syncs += 1
+
+
+def test_wait_tags_three_stages():
+    """engine.wait_tags on a numpy tag array: tags that are there return at once; tags that arrive after the spin budget are
+    found by the sleeping polls; tags that never arrive synchronise the stream once and raise with the tag and the value read."""
+    st = _Stream()
+    words = np.full(3, 7.0)
+    wait_tags(words, 7.0, st, 0.001)
+    assert st.syncs == 0
+    words[:] = 6.0
+    timer = threading.Timer(0.01, lambda: words.fill(7.0))
+    timer.start()
+    try:
+        wait_tags(words, 7.0, st, 0.001)
+    finally:
+        timer.join()
+    assert st.syncs == 0 and (words == 7.0).all()
+    words[:] = [8.0, 8.0, 5.0]
+    with pytest.raises(hip.HipError) as ei:
+        wait_tags(words, 8.0, st, 0.001, deadline=0.05)
+    assert st.syncs == 1
+    assert str(ei.value) == ('frame 8.0 never published its result block (tag reads 5.0): '
+                             'the frame graph did not run to the decode kernel')

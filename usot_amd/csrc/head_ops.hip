@@ -518,44 +518,18 @@ __global__ __launch_bounds__(256) void rows_copy_multi_kernel(const RowsK k, con
     }
 }
 
-// Append + gather in ONE launch (round 6, the session's 'defer_append' = 2 frame): the row the PREVIOUS frame pooled (bank 0)
-// and its three encodings (banks 1-3) go to row idx[slot_pos] of their banks, and the n_pick rows idx[0 .. n_pick) of banks
-// 1-3 are gathered into the frame's picked-kernel buffers - a picked row that IS the appended row is read from the new
-// row itself, so the two halves need no ordering between them.  blockIdx.y: 0-3 = append bank y, 4-6 = gather bank y - 3.
-// idx lives in pinned HOST memory (the control block): a workgroup fetches its words once.
-struct RowsAG {
-    const float *fresh[4];
-    float *bank[4];
-    float *picked[3];
-    int row_len4[4];
-    int n_pick, slot_pos;
-};
+// Append + gather in ONE launch (the session's 'defer_append' = 2 frame; RowsAG, rows_append_row, rows_gather: head_common.h):
+// the append row is idx[k.arg], the picks idx[0 .. n_pick).  idx lives in pinned HOST memory (the control block): a workgroup
+// fetches its words once.  Rows are not range-checked here.
 __global__ __launch_bounds__(256) void rows_append_gather_kernel(const RowsAG k, const int *__restrict__ idx)
 {
     __shared__ int rows[33];
     if (threadIdx.x < k.n_pick) rows[threadIdx.x] = idx[threadIdx.x];
-    if (threadIdx.x == 32) rows[32] = idx[k.slot_pos];
+    if (threadIdx.x == 32) rows[32] = idx[k.arg];
     __syncthreads();
-    const int slot = rows[32];
     const int job = blockIdx.y;
-    if (job < 4) {
-        const int rl = k.row_len4[job];
-        const f32x4 *__restrict__ src = (const f32x4 *)k.fresh[job];
-        f32x4 *__restrict__ dst = (f32x4 *)k.bank[job] + (long)slot * rl;
-        for (int i = blockIdx.x * 256 + threadIdx.x; i < rl; i += gridDim.x * 256) dst[i] = src[i];
-        return;
-    }
-    const int b = job - 3;
-    const int rl = k.row_len4[b];
-    const f32x4 *__restrict__ fresh = (const f32x4 *)k.fresh[b];
-    const f32x4 *__restrict__ bank = (const f32x4 *)k.bank[b];
-    f32x4 *__restrict__ dst = (f32x4 *)k.picked[b - 1];
-    const int total = k.n_pick * rl;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-        const int r = i / rl, e = i - r * rl;
-        const int row = rows[r];
-        dst[i] = row == slot ? fresh[e] : bank[(long)row * rl + e];
-    }
+    if (job < 4) rows_append_row(k, job, rows[32], 0);
+    else         rows_gather<false>(k, job - 3, rows, nullptr, k.n_pick, rows[32], 0, 0);
 }
 
 // The same launch on DISTINCT rows only (usot_rows_append_gather_dedupe_f32): the frame's picks repeat rows (the reference's index
@@ -569,7 +543,7 @@ __global__ __launch_bounds__(256) void rows_append_gather_dedupe_kernel(const Ro
 {
     __shared__ int rows[33], first[32], lead[32], nd;
     if (threadIdx.x < k.n_pick) rows[threadIdx.x] = idx[threadIdx.x];
-    if (threadIdx.x == 32) rows[32] = idx[k.slot_pos];
+    if (threadIdx.x == 32) rows[32] = idx[k.arg];
     __syncthreads();
     if (threadIdx.x < k.n_pick) {
         int f = threadIdx.x;
@@ -592,26 +566,9 @@ __global__ __launch_bounds__(256) void rows_append_gather_dedupe_kernel(const Ro
         if (blockIdx.x == 0 && blockIdx.y == 0) mem_map[1 + threadIdx.x] = u;
     }
     __syncthreads();
-    const int slot = rows[32];
     const int job = blockIdx.y;
-    if (job < 4) {
-        const int rl = k.row_len4[job];
-        const f32x4 *__restrict__ src = (const f32x4 *)k.fresh[job];
-        f32x4 *__restrict__ dst = (f32x4 *)k.bank[job] + (long)slot * rl;
-        for (int i = blockIdx.x * 256 + threadIdx.x; i < rl; i += gridDim.x * 256) dst[i] = src[i];
-        return;
-    }
-    const int b = job - 3;
-    const int rl = k.row_len4[b];
-    const f32x4 *__restrict__ fresh = (const f32x4 *)k.fresh[b];
-    const f32x4 *__restrict__ bank = (const f32x4 *)k.bank[b];
-    f32x4 *__restrict__ dst = (f32x4 *)k.picked[b - 1];
-    const int total = nd * rl;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
-        const int r = i / rl, e = i - r * rl;
-        const int row = rows[lead[r]];
-        dst[i] = row == slot ? fresh[e] : bank[(long)row * rl + e];
-    }
+    if (job < 4) rows_append_row(k, job, rows[32], 0);
+    else         rows_gather<false>(k, job - 3, rows, lead, nd, rows[32], 0, 0);
 }
 
 // ---- SiamFC crop on the device (lib/utils/track_utils.py:30-119): window extraction with
@@ -629,12 +586,8 @@ __global__ __launch_bounds__(256) void crop_resize_kernel(const CropK p)
 
 // ---- decode (usot_tracker.py:138-163): one workgroup, double precision like the numpy
 // reference (its grids are float64, so everything after the float32 sigmoid promotes).
-// One response cell per thread at S <= 32 (a single pass: the loads of all six maps in flight
-// together), the argmax as a wavefront butterfly + one LDS round over the waves, and the WINNING
-// thread — which still holds its cell's box, score and penalty in registers — publishes the
-// results (round 6; before: 256 threads x 3 cells, an 8-step LDS tree, thread 0 recomputing the
-// winner's cell: 10.8 us per frame in the graph).  Same expressions, same order: bit-identical.
-// DecCell and dec_better (np.argmax: first maximum, first NaN wins): head_common.h
+// The cell scan, the argmax and the result block are head_common.h's (dec_scan_argmax, dec_publish),
+// shared with the lock-step batch: same expressions, same order, bit-identical.
 __global__ __launch_bounds__(1024) void decode_kernel(
     const float *__restrict__ cls, const float *__restrict__ cls_mem, const float *__restrict__ bbox,
     const double *__restrict__ window, double *__restrict__ out, int S, int instance_size, int stride,
@@ -650,108 +603,26 @@ __global__ __launch_bounds__(1024) void decode_kernel(
         oa = ((const unsigned long long *)tsz_dev)[3];
         tag = tsz_dev[6];
     }
-    __shared__ double wave_v[16];
-    __shared__ int wave_i[16];
-    __shared__ int win_i;
-    const int n = S * S;
-    const double tpad = (tw + th) * 0.5;
-    const double tsz = sqrt((tw + tpad) * (th + tpad));
-    const double tratio = tw / th;
     DecCell best;
-    best.ps = -1e300; best.i = 0x7fffffff;
-    best.x1 = best.y1 = best.x2 = best.y2 = best.pen = 0.0; best.sc = 0.f;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const int r = i / S, c = i - r * S;
-        const double gx = (double)((c - S / 2) * stride + instance_size / 2);
-        const double gy = (double)((r - S / 2) * stride + instance_size / 2);
-        const float s0 = 1.0f / (1.0f + expf(-cls[i]));
-        const float s1 = 1.0f / (1.0f + expf(-cls_mem[i]));
-        const float sc = ratio * s0 + (1.0f - ratio) * s1;
-        const double x1 = gx - (double)bbox[i], y1 = gy - (double)bbox[n + i];
-        const double x2 = gx + (double)bbox[2 * n + i], y2 = gy + (double)bbox[3 * n + i];
-        const double w = x2 - x1, h = y2 - y1;
-        const double pad = (w + h) * 0.5;
-        double sr = sqrt((w + pad) * (h + pad)) / tsz;
-        sr = fmax(sr, 1.0 / sr);
-        double rr = tratio / (w / h);
-        rr = fmax(rr, 1.0 / rr);
-        const double pen = exp(-(rr * sr - 1.0) * penalty_k);
-        const double ps = pen * (double)sc * (1.0 - window_influence) + window[i] * window_influence;
-        if (dec_better(ps, i, best.ps, best.i)) {
-            best.ps = ps; best.i = i; best.sc = sc; best.pen = pen;
-            best.x1 = x1; best.y1 = y1; best.x2 = x2; best.y2 = y2;
+    if (!dec_scan_argmax(best, cls, cls_mem, bbox, window, S, instance_size, stride, ratio, penalty_k, window_influence, tw, th))
+        return;
+    dec_publish(best, out, roi_out, 0.f, S, instance_size, stride);
+    if (tsz_dev) {
+        // tsz_dev[3] (as a 64-bit integer): 0, or the address of the frame's sticky split-fp16 "a sum was not finite" word
+        // (usot_conv_desc.ovf).  Its value travels with the results (out[9]) and the word is cleared for the next frame.
+        if (oa) {                                 // (then `out` has 10 doubles)
+            int *f = (int *)(uintptr_t)oa;
+            out[9] = (double)__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(f, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-    }
-    double rv = best.ps;
-    int ri = best.i;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ov = __shfl_xor(rv, off, 64);
-        const int oi = __shfl_xor(ri, off, 64);
-        if (dec_better(ov, oi, rv, ri)) { rv = ov; ri = oi; }
-    }
-    const int wv = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-    if ((threadIdx.x & 63) == 0) { wave_v[wv] = rv; wave_i[wv] = ri; }
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        rv = threadIdx.x < nw ? wave_v[threadIdx.x] : -1e300;
-        ri = threadIdx.x < nw ? wave_i[threadIdx.x] : 0x7fffffff;
-#pragma unroll
-        for (int off = 8; off > 0; off >>= 1) {
-            const double ov = __shfl_xor(rv, off, 64);
-            const int oi = __shfl_xor(ri, off, 64);
-            if (dec_better(ov, oi, rv, ri)) { rv = ov; ri = oi; }
-        }
-        if (threadIdx.x == 0) win_i = ri;
-    }
-    __syncthreads();
-    // `win_i` is a valid cell whatever the maps hold (every cell beats "no cell"); its owner publishes
-    if (best.i == win_i) {
-        out[0] = (double)best.i;
-        out[1] = (double)best.sc;
-        out[2] = best.pen;
-        out[3] = best.x1; out[4] = best.y1; out[5] = best.x2; out[6] = best.y2;
-        out[7] = best.ps;
-        if (roi_out) {
-            // usot_tracker.py:329-350 (pool_label_search): the S-point axis of the response
-            // map applied to the search feature; box rounded to float32 first (np.array(...,
-            // np.float32)), arithmetic in float64, result stored as float32 (.float()).
-            const double lo = (double)((0 - S / 2) * stride + instance_size / 2);
-            const double hi = (double)((S - 1 - S / 2) * stride + instance_size / 2);
-            const double slope = (double)(2 * (S / 2)) / (hi - lo);
-            const double gap = 1.0 / slope;
-            const double bx[4] = {best.x1, best.y1, best.x2, best.y2};
-            roi_out[0] = 0.f;
-            for (int e = 0; e < 4; ++e) {
-                double v = (double)(float)bx[e];
-                v = v < lo - gap ? lo - gap : (v > hi + gap ? hi + gap : v);      // np.clip: a NaN stays a NaN (fmax / fmin would drop it)
-                roi_out[1 + e] = (float)((v - lo) * slope);
-            }
-        }
-        if (tsz_dev) {
-            // tsz_dev[3] (as a 64-bit integer): 0, or the address of the frame's sticky split-fp16 "a sum was not finite" word
-            // (usot_conv_desc.ovf).  Its value travels with the results (out[9]) and the word is cleared for the next frame.
-            if (oa) {                                 // (then `out` has 10 doubles)
-                int *f = (int *)(uintptr_t)oa;
-                out[9] = (double)__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(f, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            // completion tag for a host that polls the (pinned, coherent) result block instead of
-            // waiting for the whole stream: results first, system-scope fence, then the tag
-            __threadfence_system();
-            out[8] = tag;
-        }
+        // completion tag for a host that polls the (pinned, coherent) result block instead of
+        // waiting for the whole stream: results first, system-scope fence, then the tag
+        __threadfence_system();
+        out[8] = tag;
     }
 }
 
 }  // namespace
-
-// one thread per response cell up to 1024 cells (S <= 32), whole wavefronts
-static inline unsigned decode_threads(int S)
-{
-    const int n = S * S;
-    return (unsigned)(n >= 1024 ? 1024 : (n + 63) / 64 * 64);
-}
 
 extern "C" int usot_conf_fusion_reduce_f32(void *stream, const float *cv, float *out,
                                            int B, int M, int P, int C)
@@ -1012,7 +883,7 @@ static int rows_append_gather_impl(void *stream, const float *const *fresh, floa
         if (t > most) most = t;
     }
     if (most > 0x3fffffffL) return USOT_EINVAL;
-    k.n_pick = n_pick; k.slot_pos = slot_pos;
+    k.n_pick = n_pick; k.arg = slot_pos;
     const int blocks = (int)((most + 255) / 256 > 64 ? 64 : (most + 255) / 256);
     if (mem_map) hipLaunchKernelGGL(rows_append_gather_dedupe_kernel, dim3(blocks, 7), dim3(256), 0, (hipStream_t)stream, k, (const int *)idx_dev, (int *)mem_map);
     else         hipLaunchKernelGGL(rows_append_gather_kernel, dim3(blocks, 7), dim3(256), 0, (hipStream_t)stream, k, (const int *)idx_dev);

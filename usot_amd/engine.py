@@ -1820,7 +1820,130 @@ class Engine:
         return BatchSession(self, p, window, slots, capacity=capacity, backbone_dtype=backbone_dtype)
 
 
-class Session:
+class MemoryBank(object):
+    """The memory features of `slots` videos and their three kernel-side encodings: four tensors of slots x cap rows each
+    (`feat` [slots * cap, 7, 7, 256] and `enc[g]` per KGEO); slot b's row r is global row b * cap + r.  Session is slots = 1."""
+
+    def __init__(self, slots, cap, device):
+        self.slots, self.cap, self.device = int(slots), int(cap), device
+        self.feat = torch.zeros(self.slots * self.cap, 7, 7, 256, device=device)
+        self.enc = [torch.zeros(self.slots * self.cap, hk, wk, 256, device=device) for hk, wk in KGEO]
+        self._enc_plans, self._enc_split = {}, None
+
+    def grow(self):
+        """Double every slot's rows: old row r of slot b moves to b * 2 cap + r, the new rows are zero."""
+        old, new, B = self.cap, self.cap * 2, self.slots
+        grown = [torch.zeros((B * new,) + tuple(t.shape[1:]), device=self.device) for t in [self.feat] + self.enc]
+        for g, t in zip(grown, [self.feat] + self.enc):
+            g.view(B, new, -1)[:, :old].copy_(t.view(B, old, -1))
+        self.feat, self.enc, self.cap = grown[0], grown[1:], new
+
+    def marshal(self, enc_only=False):
+        """(bank addresses, row lengths in floats) as the append / gather / rows_copy_multi adders take them."""
+        banks = self.enc if enc_only else [self.feat] + self.enc
+        return (C.c_void_p * len(banks))(*[t.data_ptr() for t in banks]), (C.c_int32 * len(banks))(*[int(t[0].numel()) for t in banks])
+
+    def write(self, row, feat):                          # feat: NCHW-shaped [1, 256, 7, 7], any device or strides
+        self.feat[row].copy_(hip.to_nhwc(_as_dev_f32(feat, self.device))[0])
+
+    def view(self, row):                                 # the row as an NCHW-shaped view [1, 256, 7, 7]
+        return self.feat[row:row + 1].permute(0, 3, 1, 2)
+
+    def encode(self, engine, opt, lo, n, on_overflow=None):
+        """Encode rows [lo, lo + n) into the encoding banks through one cached plan per row count, built under `opt`.  A split-fp16
+        plan's range word is read after every run: on overflow on_overflow() turns opt['split16_f32'] off, which drops the cache."""
+        if self._enc_split != bool(opt['split16_f32']):
+            self._enc_plans, self._enc_split = {}, bool(opt['split16_f32'])
+        if n not in self._enc_plans:
+            bld = Builder(engine.W, engine.tuning, 0, opt)
+            src = bld.buf(n, 7, 7, 256)
+            self._enc_plans[n] = (bld.plan, src, bld.encode_kernel(src, n, 256, 'mem'), bld.ovf)
+        plan, src, enc, ovf = self._enc_plans[n]
+        src.copy_(self.feat[lo:lo + n])
+        plan.run()
+        if ovf is not None and int(ovf.item()):         # (a stream synchronisation)
+            on_overflow()
+            return self.encode(engine, opt, lo, n, on_overflow)
+        for g in range(3):
+            self.enc[g][lo:lo + n].copy_(enc[g])
+
+
+def wait_tags(words, tag, stream, spin_seconds, deadline=20.0):
+    """Wait until every word of `words` (a numpy view of the pinned tag words the decode kernel writes behind its results) reads
+    `tag`: spin for spin_seconds (several frame times), then give the core away between polls for `deadline` seconds, then drain
+    `stream` and look once more.  The words are waited for in turn with scalar compares (45 ns each).  The spin budget is wall-clock,
+    read once per 512 polls: a fixed poll count once ran out right around a frame's end, and each such frame paid a 50 us sleep."""
+    n, i = len(words), 0
+    spin_until, spinning = time.perf_counter() + spin_seconds, True
+    while spinning:
+        for _ in range(512):
+            if words[i] == tag:
+                i += 1
+                if i == n:
+                    return
+        spinning = time.perf_counter() < spin_until
+    end, drained = time.monotonic() + deadline, False
+    while True:
+        while words[i] == tag:
+            i += 1
+            if i == n:
+                return
+        if drained:
+            raise hip.HipError('frame %r never published its result block (tag reads %r): '
+                               'the frame graph did not run to the decode kernel' % (tag, float(words[i])))
+        if time.monotonic() < end:
+            time.sleep(5e-5)
+        else:
+            stream.synchronize()
+            drained = True
+
+
+class ImageStage(object):
+    """One uint8 HWC frame on its way to the device: a pinned host buffer and a device buffer, reallocated when the shape changes."""
+    dev = None
+
+    def upload(self, im, device):
+        h, w, _ = im.shape
+        if self.dev is None or tuple(self.dev.shape) != (h, w, 3):
+            self.dev = torch.empty((h, w, 3), dtype=torch.uint8, device=device)
+            self.host = torch.empty((h, w, 3), dtype=torch.uint8).pin_memory()
+            self._host_np = self.host.numpy()
+        # numpy memcpy into the pinned staging buffer: torch's CPU copy_ fans out over every
+        # hardware thread it sees (5.6 ms for 0.5 MB under a 16-CPU cgroup quota on a 256-thread host)
+        np.copyto(self._host_np, im)
+        self.dev.copy_(self.host, non_blocking=True)
+        return self.dev
+
+
+def crop_fields(im_shape, pos, win, avg_chans):
+    """(x0, y0, win, fill): the window origin in image coordinates and the padding colour (numpy's float -> uint8 truncates)."""
+    from .hostutils import crop_geometry
+    (cx0, _, cy0, _), (top, _, left, _) = crop_geometry(im_shape, pos, win)
+    fill = np.asarray(avg_chans).astype(np.uint8)
+    return int(cx0) - left, int(cy0) - top, int(win), (int(fill[0]), int(fill[1]), int(fill[2]))
+
+
+class _BankSession(object):
+    """What Session and BatchSession share besides the helpers above: the bank's tensors under their names and two plan pieces."""
+    bank = property(lambda self: self.mem.feat)
+    bank_enc = property(lambda self: self.mem.enc)
+
+    def _add_prroi(self, pl, xf, n, hf):
+        """PrRoIPool 7 x 7 of the n decoded boxes self.roi on the NHWC neck map xf [n, hf, hf, 256] into the NHWC features self.feat."""
+        c = 256
+        hip.check(hip.lib().usot_plan_add_prroi(pl.h, hip.ptr(xf), hip.ptr(self.roi), hip.ptr(self.feat), n, c, hf, hf, 7, 7, 1.0,
+                                                hf * hf * c, 1, hf * c, c, 49 * c, 1, 7 * c, c), 'plan_add_prroi')
+
+    def _build_flush_plan(self, opt, n, add_append, keep):
+        """flush(): encode the n pooled features self.feat and append them (add_append(plan, [feat] + encodings)) as a plan of its own."""
+        fb = Builder(self.e.W, self.e.tuning, 0, opt)
+        fenc = fb.encode_kernel(self.feat, n, 256, 'mem')
+        add_append(fb.plan, [self.feat] + fenc)
+        fb.plan.keep += fenc + [self.feat] + keep
+        return fb.plan
+
+
+class Session(_BankSession):
     """One video's state kept in HBM + its per-frame launch plan (a captured hipGraph).
 
     bank rows: 0 = init-frame feature, 1 = its left/right flip, 2+i = memory feature i
@@ -1837,8 +1960,6 @@ class Session:
     kernels address directly).  'defer_append' = 0 is the in-frame form: gather -> backbone -> ... -> PrRoIPool -> encode -> scatter.
     """
 
-    ROW = 7 * 7 * 256
-
     def __init__(self, engine, p, window, init_feats, capacity=1024):
         self.e = engine
         self.p = p
@@ -1846,11 +1967,9 @@ class Session:
         self.size, self.S = int(p.instance_size), int(p.score_size)
         self.zk = [t.clone() for t in engine._zenc[1]['zk']]
         self.window = torch.from_numpy(np.ascontiguousarray(window, dtype=np.float64)).reshape(-1).to(dev)
-        self.cap = capacity
-        self.bank = torch.zeros(capacity, 7, 7, 256, device=dev)
+        self.mem = MemoryBank(1, capacity, dev)
         for i, f in enumerate((init_feats[0], init_feats[1], init_feats[0])):
-            self.bank[i].copy_(hip.to_nhwc(f)[0])
-        self.bank_enc = [torch.zeros(capacity, hk, wk, 256, device=dev) for hk, wk in KGEO]
+            self.mem.write(i, f)
         self._encode_rows(0, 3)
         self.n = 1                                   # memory features stored so far
         # Control and result blocks live in pinned (device-mapped, coherent) HOST memory that the
@@ -1866,7 +1985,10 @@ class Session:
         self.out8 = torch.zeros(16, dtype=torch.float64).pin_memory()   # 8 results + completion tag
         self.x_host = torch.zeros(1, 3, self.size, self.size).pin_memory()
         self._x_host_np = self.x_host.numpy()
+        self._image = ImageStage()
         self._build()
+
+    cap = property(lambda self: self.mem.cap)
 
     def _build(self):
         e, L = self.e, hip.lib()
@@ -1918,10 +2040,9 @@ class Session:
             if new_enc is None:                      # no stand-alone shortcut conv took them (other lowering options): own launch
                 bld.piggyback = None
                 new_enc = bld.encode_kernel(self.feat, 1, 256, 'mem')
-            fresh, banks = [self.feat] + new_enc, [self.bank] + self.bank_enc
-            rl = [int(b[0].numel()) for b in banks]
-            ag = (pl.h, (C.c_void_p * 4)(*[t.data_ptr() for t in fresh]), (C.c_void_p * 4)(*[t.data_ptr() for t in banks]),
-                  (C.c_void_p * 3)(*[t.data_ptr() for t in mk]), (C.c_int32 * 4)(*rl), hip.ptr(idx_dev), nq, nq + 3)
+            banks, rl = self.mem.marshal()
+            ag = (pl.h, (C.c_void_p * 4)(*[t.data_ptr() for t in [self.feat] + new_enc]), banks,
+                  (C.c_void_p * 3)(*[t.data_ptr() for t in mk]), rl, hip.ptr(idx_dev), nq, nq + 3)
             if self.dedupe:
                 for t in mk:
                     t.zero_()       # rows >= D of the picked kernels are never written, and never read: defined all the same
@@ -1931,8 +2052,8 @@ class Session:
         elif self.defer:
             pl.fork(3)
             new_enc = bld.encode_kernel(self.feat, 1, 256, 'mem')       # the PREVIOUS frame's pooled feature
-            self._rows_multi(pl, [self.feat] + new_enc, idx_dev[nq + 3:], [self.bank] + self.bank_enc, 1, scatter=1)
-            self._rows_multi(pl, self.bank_enc, idx_dev, mk, nq, scatter=0, stash=self.slot_dev)
+            self._rows_multi(pl, [self.feat] + new_enc, idx_dev[nq + 3:], 1, scatter=1)
+            self._rows_multi(pl, mk, idx_dev, nq, scatter=0, stash=self.slot_dev)
             pl.fork(0)
             xf, hf = bld.backbone(self.x, 1, self.size, need_stem=False, xptr_dev=idx_dev[nq + 1:nq + 3])
             pl.join(3)
@@ -1940,7 +2061,7 @@ class Session:
             # the append row of this frame is stashed in device memory: the scatter at the end of
             # the graph runs AFTER the result tag the host waits for, i.e. possibly while the host is
             # already writing the next frame's control block
-            self._rows_multi(pl, self.bank_enc, idx_dev, mk, nq, scatter=0, stash=self.slot_dev)
+            self._rows_multi(pl, mk, idx_dev, nq, scatter=0, stash=self.slot_dev)
             # slot_dev[0] = the append row, slot_dev[1:3] = the crop's address: both stashed from the control block by the
             # gather above (the first kernel of the frame)
             xf, hf = bld.backbone(self.x, 1, self.size, need_stem=False, xptr_dev=self.slot_dev[1:3])
@@ -1952,20 +2073,15 @@ class Session:
                                          hip.ptr(self.out8), S, self.size, int(p.total_stride), float(p.ratio),
                                          float(p.penalty_k), float(p.window_influence), hip.ptr(tsz_dev),
                                          hip.ptr(self.roi)), 'plan_add_decode')
-        c = 256
-        hip.check(L.usot_plan_add_prroi(pl.h, hip.ptr(xf), hip.ptr(self.roi), hip.ptr(self.feat), 1, c, hf, hf, 7, 7, 1.0,
-                                        hf * hf * c, 1, hf * c, c, 49 * c, 1, 7 * c, c), 'plan_add_prroi')
+        self._add_prroi(pl, xf, 1, hf)
         if not self.defer:
             new_enc = bld.encode_kernel(self.feat, 1, 256, 'mem')       # the new feature's encodings, once
-            self._rows_multi(pl, [self.feat] + new_enc, self.slot_dev, [self.bank] + self.bank_enc, 1, scatter=1)
+            self._rows_multi(pl, [self.feat] + new_enc, self.slot_dev, 1, scatter=1)
         else:
             # flush(): the same append as a small plan of its own, its row read from a pinned word
-            fb = Builder(e.W, e.tuning, 0, e.opt)
             self._flush_idx = torch.zeros(2, dtype=torch.int32).pin_memory()
-            fenc = fb.encode_kernel(self.feat, 1, 256, 'mem')
-            self._rows_multi(fb.plan, [self.feat] + fenc, self._flush_idx, [self.bank] + self.bank_enc, 1, scatter=1)
-            fb.plan.keep += fenc + [self.feat, self._flush_idx, self.bank] + self.bank_enc
-            self._flush_plan = fb.plan
+            self._flush_plan = self._build_flush_plan(e.opt, 1, lambda fpl, fresh: self._rows_multi(fpl, fresh, self._flush_idx, 1, 1),
+                                                      [self._flush_idx, self.bank] + self.bank_enc)
         pl.keep += mk + new_enc + self.bank_enc + [self.slot_dev, self.mem_map]
         pl.keep += [self.bank, self.ctl, self.window, self.out8, tsz_dev, idx_dev] + self.zk
         self.xf, self.cls2, self.bbox, self.plan, self._log = xf, cls2, bbox, pl, bld.log
@@ -2012,28 +2128,17 @@ class Session:
             self._flush_plan.run()
         st.synchronize()
 
-    @staticmethod
-    def _rows_multi(pl, srcs, idx, dsts, n_rows, scatter, stash=None):
-        n = len(srcs)
-        rl = [int(bank[0].numel()) for bank in (dsts if scatter else srcs)]      # row = one bank entry
+    def _rows_multi(self, pl, bufs, idx, n_rows, scatter, stash=None):
+        """Bank rows idx[0 .. n_rows): scatter = 1 writes them from `bufs` (feature + encodings), 0 gathers the encodings into `bufs`."""
+        banks, rl = self.mem.marshal(enc_only=not scatter)
+        mine = (C.c_void_p * len(bufs))(*[t.data_ptr() for t in bufs])
         hip.check(hip.lib().usot_plan_add_rows_copy_multi(
-            pl.h, n, (C.c_void_p * n)(*[t.data_ptr() for t in srcs]), hip.ptr(idx),
-            (C.c_void_p * n)(*[t.data_ptr() for t in dsts]), n_rows, (C.c_int32 * n)(*rl), scatter,
+            pl.h, len(bufs), mine if scatter else banks, hip.ptr(idx), banks if scatter else mine, n_rows, rl, scatter,
             hip.ptr(stash) if stash is not None else None), 'plan_add_rows_copy_multi')
 
     def _encode_rows(self, lo, hi):
-        """Encode bank rows [lo, hi) into bank_enc (session start: init feature, its flip, memory 0)."""
-        bld = Builder(self.e.W, self.e.tuning, 0, self.e.opt)
-        src = bld.buf(hi - lo, 7, 7, 256)
-        src.copy_(self.bank[lo:hi])
-        enc = bld.encode_kernel(src, hi - lo, 256, 'mem')
-        bld.plan.run()
-        torch.cuda.current_stream().synchronize()
-        if bld.ovf is not None and int(bld.ovf.item()):
-            self.e._to_exact('Session: memory-feature encoders')
-            return self._encode_rows(lo, hi)
-        for g in range(3):
-            self.bank_enc[g][lo:hi].copy_(enc[g])
+        """Encode bank rows [lo, hi) into bank_enc (session start: init feature, its flip, memory 0) under the engine's options."""
+        self.mem.encode(self.e, self.e.opt, lo, hi - lo, lambda: self.e._to_exact('Session: memory-feature encoders'))
         torch.cuda.current_stream().synchronize()
 
     def _set_ctl(self, rows, slot, tsz, xaddr=0):
@@ -2056,12 +2161,7 @@ class Session:
 
     def _grow(self):
         self.flush()
-        bank = torch.zeros(self.cap * 2, 7, 7, 256, device=self.e.device)
-        bank[:self.cap].copy_(self.bank)
-        enc = [torch.zeros(self.cap * 2, hk, wk, 256, device=self.e.device) for hk, wk in KGEO]
-        for g in range(3):
-            enc[g][:self.cap].copy_(self.bank_enc[g])
-        self.bank, self.bank_enc, self.cap = bank, enc, self.cap * 2
+        self.mem.grow()
         self._build()
 
     def submit(self, x_crop, picks, tsz_scaled, resident=False, inplace=False):
@@ -2110,7 +2210,9 @@ class Session:
         rather than sleeping in hipStreamSynchronize (the PrRoIPool + bank append behind it are
         ordered before the next frame by the stream)."""
         try:
-            out = self._collect()
+            wait_tags(self._out_np[8:9], self._tag, self._stream, self.e.opt['spin_seconds'])
+            if self._ovf is not None and self._out_np[9] != 0.0:
+                self._rerun_exact()                 # split-fp16 range contract broken by this frame: the same frame on the exact-fp32 tiles
         except BaseException:
             # a frame that never published its tag may still be running and reads the in-place crop by ADDRESS: drain the
             # stream before the reference (the only thing keeping that memory away from the caching allocator) is dropped
@@ -2120,7 +2222,9 @@ class Session:
                 self._x_ref = None
             raise
         self._x_ref = None                          # the tag was observed: the crop may be reused from here on
-        return out
+        self._prev_slot, self._pending = 2 + self.n, True      # ('defer_append': this frame's row, written by the next graph)
+        self.n += 1
+        return self._out_np[:8].copy()
 
     def _rerun_exact(self):
         """The frame just collected saw an activation beyond the split-fp16 window (out[9]): rebuild this session's frame graph on
@@ -2145,36 +2249,6 @@ class Session:
         if self._out_np[8] != self._tag:
             raise hip.HipError('frame %r: the exact-fp32 re-run never published its result block' % (self._tag,))
 
-    def _collect(self):
-        out, tag = self._out_np, self._tag
-        # spin for SPIN_SECONDS (several frame times), then give the core away between polls.  The budget is wall-clock: a
-        # fixed 20 000 polls turned out to be 0.905 ms on this host (45 ns per numpy compare), i.e. it ran out right around
-        # the end of a 0.86 ms frame and every such frame then paid a 50 us sleep and a launch onto an idle queue
-        spin_until = time.perf_counter() + self.e.opt['spin_seconds']
-        while True:
-            for _ in range(512):
-                if out[8] == tag:
-                    break
-            else:
-                if time.perf_counter() < spin_until:
-                    continue
-            break
-        if out[8] != tag:
-            deadline = time.monotonic() + 20.0
-            while out[8] != tag and time.monotonic() < deadline:
-                time.sleep(5e-5)
-            if out[8] != tag:
-                self._stream.synchronize()
-                if out[8] != tag:
-                    raise hip.HipError('frame %r never published its result block (tag reads %r): '
-                                       'the frame graph did not run to the decode kernel' % (tag, float(out[8])))
-        if self._ovf is not None and out[9] != 0.0:
-            self._rerun_exact()                     # split-fp16 range contract broken by this frame: the same frame on the exact-fp32 tiles
-            out = self._out_np
-        self._prev_slot, self._pending = 2 + self.n, True      # ('defer_append': this frame's row, written by the next graph)
-        self.n += 1
-        return out[:8].copy()
-
     def append_feature(self, feat):
         """Append a memory feature computed OUTSIDE the frame graph (NCHW-shaped [1,256,7,7], any strides):
         bank row + its three kernel-side encodings.  Lets a caller that switches from the fused path to
@@ -2183,7 +2257,7 @@ class Session:
         self.flush()
         torch.cuda.current_stream().synchronize()
         row = 2 + self.n
-        self.bank[row].copy_(hip.to_nhwc(_as_dev_f32(feat, self.e.device))[0])
+        self.mem.write(row, feat)
         self._encode_rows(row, row + 1)
         self.n += 1
 
@@ -2197,27 +2271,16 @@ class Session:
         """Whole frame from the raw image: upload the uint8 frame, crop/pad/resize on the
         device straight into the plan's input buffer (hostutils.get_subwindow_tracking's
         arithmetic), then `frame`.  `win` = python2round(s_x)."""
-        from .hostutils import crop_geometry
         self._ensure_capacity()
-        h, w, _ = im.shape
-        if getattr(self, '_im_dev', None) is None or tuple(self._im_dev.shape) != (h, w, 3):
-            self._im_dev = torch.empty((h, w, 3), dtype=torch.uint8, device=self.e.device)
-            self._im_host = torch.empty((h, w, 3), dtype=torch.uint8).pin_memory()
-            self._im_host_np = self._im_host.numpy()
-        # numpy memcpy into the pinned staging buffer: torch's CPU copy_ fans out over every
-        # hardware thread it sees (5.6 ms for 0.5 MB under a 16-CPU cgroup quota on a 256-thread host)
-        np.copyto(self._im_host_np, im)
-        self._im_dev.copy_(self._im_host, non_blocking=True)
-        (cx0, _, cy0, _), (top, _, left, _) = crop_geometry(im.shape, pos, win)
-        fill = np.asarray(avg_chans).astype(np.uint8)         # numpy's float -> uint8 assignment truncates
-        hip.crop_resize(self._im_dev, self.x[0], int(cx0) - left, int(cy0) - top, int(win), fill)
+        x0, y0, win, fill = crop_fields(im.shape, pos, win, avg_chans)
+        hip.crop_resize(self._image.upload(im, self.e.device), self.x[0], x0, y0, win, fill)
         return self.frame(None, picks, tsz_scaled, resident=True)
 
     def memory_feature(self, i):
         """Memory feature i as an NCHW-shaped view [1,256,7,7] of its bank row."""
         if i == self.n - 1:
             self.flush()
-        return self.bank[2 + i:3 + i].permute(0, 3, 1, 2)
+        return self.mem.view(2 + i)
 
 
 class MemoryFeatures(object):
@@ -2259,15 +2322,6 @@ SLOT_REC = np.dtype([('tsz', '<f8', (2,)), ('im', '<u8'), ('H', '<i4'), ('W', '<
                      ('fill', '<i4', (3,)), ('append_row', '<i4'), ('next_row', '<i4'), ('picks', '<i4', (32,))])
 assert SLOT_REC.itemsize == 192 and SLOT_REC.fields['append_row'][1] == 56 and SLOT_REC.fields['picks'][1] == 64
 IDLE_TSZ = (64.0, 64.0)         # target size of a slot that sits a step out (its results are not read)
-
-
-def crop_fields(im_shape, pos, win, avg_chans):
-    """(x0, y0, win, fill) of a slot's crop record: the window origin in image coordinates (hostutils.crop_geometry, as
-    Session.frame_from_image computes it) and the padding colour (numpy's float -> uint8 assignment truncates)."""
-    from .hostutils import crop_geometry
-    (cx0, _, cy0, _), (top, _, left, _) = crop_geometry(im_shape, pos, win)
-    fill = np.asarray(avg_chans).astype(np.uint8)
-    return int(cx0) - left, int(cy0) - top, int(win), (int(fill[0]), int(fill[1]), int(fill[2]))
 
 
 class SlotBook(object):
@@ -2379,7 +2433,7 @@ class SlotBook(object):
         self.prev_row = [self.scratch(b) for b in range(self.B)]
 
 
-class BatchSession:
+class BatchSession(_BankSession):
     """B videos ("slots") of one instance size in HBM + ONE captured frame graph that steps all of them (lock-step tracking).
 
     A step (lanes = 0, nothing forked):
@@ -2390,8 +2444,6 @@ class BatchSession:
     The backbone and heads are exact fp32 whatever the engine's split16_f32 (the graph has no range word); opt-in
     backbone_dtype=torch.float16 puts the fp16 backbone with an fp32 neck in front of the same fp32 heads.  The step's control
     block (STEP_HDR + B SLOT_REC records) and the result rows live in pinned host memory the kernels address directly."""
-
-    ROW = 7 * 7 * 256
 
     def __init__(self, engine, p, window, slots, capacity=1024, backbone_dtype=torch.float32):
         if backbone_dtype not in (torch.float32, torch.float16):
@@ -2410,9 +2462,7 @@ class BatchSession:
         self.opt['split16_f32'] = False                 # exact fp32 arithmetic: the step graph has no range word
         self.window = torch.from_numpy(np.ascontiguousarray(window, dtype=np.float64)).reshape(-1).to(dev)
         self.book = SlotBook(self.B, capacity, self.nq)
-        cap = capacity
-        self.bank = torch.zeros(self.B * cap, 7, 7, 256, device=dev)
-        self.bank_enc = [torch.zeros(self.B * cap, hk, wk, 256, device=dev) for hk, wk in KGEO]
+        self.mem = MemoryBank(self.B, capacity, dev)
         self.zk = [torch.zeros(self.B, hk, wk, 512, device=dev) for hk, wk in KGEO]
         nbytes = STEP_HDR + self.B * SLOT_REC.itemsize
         self.ctl = torch.zeros(nbytes, dtype=torch.uint8).pin_memory()
@@ -2422,24 +2472,18 @@ class BatchSession:
         self._frecs = self.fctl.numpy()[STEP_HDR:].view(SLOT_REC)
         self.out = torch.zeros(self.B, 16, dtype=torch.float64).pin_memory()   # per slot: 8 results, the tag at [8]
         self._out_np = self.out.numpy()
-        self._im_dev = [None] * self.B
-        self._im_host = [None] * self.B
+        self._images = [ImageStage() for _ in range(self.B)]
         self._step = 0
         self._items = []
-        self._lenc = None
         self._build()
 
-    @property
-    def cap(self):
-        return self.book.cap
+    cap = property(lambda self: self.book.cap)
 
     def _append_gather(self, pl, fresh, ctl):
-        banks = [self.bank] + self.bank_enc
-        rl = [int(b[0].numel()) for b in banks]
+        banks, rl = self.mem.marshal()
         hip.check(hip.lib().usot_plan_add_rows_append_gather_batch(
-            pl.h, (C.c_void_p * 4)(*[t.data_ptr() for t in fresh]), (C.c_void_p * 4)(*[t.data_ptr() for t in banks]),
-            (C.c_void_p * 3)(*[t.data_ptr() for t in self.mk]), (C.c_int32 * 4)(*rl), hip.ptr(ctl), self.B, self.nq,
-            int(self.bank.shape[0])), 'plan_add_rows_append_gather_batch')
+            pl.h, (C.c_void_p * 4)(*[t.data_ptr() for t in fresh]), banks, (C.c_void_p * 3)(*[t.data_ptr() for t in self.mk]), rl,
+            hip.ptr(ctl), self.B, self.nq, int(self.bank.shape[0])), 'plan_add_rows_append_gather_batch')
 
     def _build(self):
         e, L, B, nq, p = self.e, hip.lib(), self.B, self.nq, self.p
@@ -2465,17 +2509,12 @@ class BatchSession:
                                                hip.ptr(self.out), B, S, self.size, int(p.total_stride), float(p.ratio),
                                                float(p.penalty_k), float(p.window_influence), hip.ptr(self.ctl),
                                                hip.ptr(self.roi)), 'plan_add_decode_batch')
-        c = 256
-        hip.check(L.usot_plan_add_prroi(pl.h, hip.ptr(xf), hip.ptr(self.roi), hip.ptr(self.feat), B, c, hf, hf, 7, 7, 1.0,
-                                        hf * hf * c, 1, hf * c, c, 49 * c, 1, 7 * c, c), 'plan_add_prroi')
+        self._add_prroi(pl, xf, B, hf)
         if bld.ovf is not None:
             raise hip.HipError('BatchSession: the step graph has a split-fp16 range word')
         # flush(): the same encode launch (n = B) and the same append kernel, reading its own control block
-        fb = Builder(e.W, e.tuning, 0, self.opt)
-        fenc = fb.encode_kernel(self.feat, B, 256, 'mem')
-        self._append_gather(fb.plan, [self.feat] + fenc, self.fctl)
-        fb.plan.keep += fenc + [self.feat, self.fctl, self.bank] + self.bank_enc + self.mk
-        self._flush_plan = fb.plan
+        self._flush_plan = self._build_flush_plan(self.opt, B, lambda fpl, fresh: self._append_gather(fpl, fresh, self.fctl),
+                                                  [self.fctl, self.bank] + self.bank_enc + self.mk)
         pl.keep += enc + self.mk + self.bank_enc + self.zk + [self.bank, self.ctl, self.window, self.out, self.roi, self.feat]
         self.xf, self.cls2, self.bbox, self.hf, self.plan, self.log = xf, cls2, bbox, hf, pl, bld.log
         # warm-up replay (Engine._finish): every slot idle, appends to the scratch rows
@@ -2485,19 +2524,6 @@ class BatchSession:
         torch.cuda.current_stream().synchronize()
         self.feat.zero_()
         torch.cuda.current_stream().synchronize()
-
-    def _encode_rows(self, rows):
-        """Encode bank rows `rows` (global, 3 of them) into bank_enc on the exact-fp32 encoders."""
-        if self._lenc is None:
-            bld = Builder(self.e.W, self.e.tuning, 0, self.opt)
-            src = bld.buf(3, 7, 7, 256)
-            enc = bld.encode_kernel(src, 3, 256, 'mem')
-            self._lenc = (bld.plan, src, enc)
-        plan, src, enc = self._lenc
-        src.copy_(self.bank[rows[0]:rows[-1] + 1])
-        plan.run()
-        for g in range(3):
-            self.bank_enc[g][rows[0]:rows[-1] + 1].copy_(enc[g])
 
     def load(self, slot, zf, init_feats):
         """A new video in `slot`: its template kernels (Engine.encode_template at n = 1 of zf, NCHW-shaped [1,256,7,7]) and the
@@ -2511,8 +2537,8 @@ class BatchSession:
             self.zk[g][slot].copy_(zk[g][0])
         base = self.book.row(slot, 0)
         for i, f in enumerate((init_feats[0], init_feats[1], init_feats[0])):
-            self.bank[base + i].copy_(hip.to_nhwc(_as_dev_f32(f, self.e.device))[0])
-        self._encode_rows([base, base + 1, base + 2])
+            self.mem.write(base + i, f)
+        self.mem.encode(self.e, self.opt, base, 3)            # on the exact-fp32 encoders
         self.book.load(slot)
 
     def release(self, slot):
@@ -2521,15 +2547,7 @@ class BatchSession:
     def _grow(self):
         self.flush()
         torch.cuda.current_stream().synchronize()
-        old, B, dev = self.book.cap, self.B, self.e.device
-        new = old * 2
-
-        def regrow(t):
-            g = torch.zeros((B * new,) + tuple(t.shape[1:]), device=dev)
-            g.view(B, new, -1)[:, :old].copy_(t.view(B, old, -1))
-            return g
-        self.bank = regrow(self.bank)
-        self.bank_enc = [regrow(t) for t in self.bank_enc]
+        self.mem.grow()
         self.book.grow()
         self._build()
 
@@ -2548,13 +2566,8 @@ class BatchSession:
             book_items[b] = (it['picks'], it['tsz'])
             if it.get('image') is not None:
                 im = it['image']
-                h, w, _ = im.shape
-                if self._im_dev[b] is None or tuple(self._im_dev[b].shape) != (h, w, 3):
-                    self._im_dev[b] = torch.empty((h, w, 3), dtype=torch.uint8, device=self.e.device)
-                    self._im_host[b] = torch.empty((h, w, 3), dtype=torch.uint8).pin_memory()
-                np.copyto(self._im_host[b].numpy(), im)
-                self._im_dev[b].copy_(self._im_host[b], non_blocking=True)
-                crops[b] = (self._im_dev[b].data_ptr(), h, w) + crop_fields(im.shape, it['pos'], it['win'], it['avg_chans'])
+                crops[b] = (self._images[b].upload(im, self.e.device).data_ptr(), im.shape[0], im.shape[1]) + \
+                    crop_fields(im.shape, it['pos'], it['win'], it['avg_chans'])
             elif it.get('crop') is not None:
                 self.x[b].copy_(torch.as_tensor(it['crop']).reshape(3, self.size, self.size))
         self.book.pack(self._recs, book_items, crops)
@@ -2567,21 +2580,8 @@ class BatchSession:
     def collect(self):
         """Wait for every slot's tag of the submitted step; {slot: float64[8]} (Session.collect's layout) of the slots that
         stepped."""
-        out, tag = self._out_np, self._tag[0]
-        tags = out[:, 8]
-        spin_until = time.perf_counter() + self.e.opt['spin_seconds']
-        while not (tags == tag).all() and time.perf_counter() < spin_until:
-            pass
-        if not (tags == tag).all():
-            deadline = time.monotonic() + 20.0
-            while not (tags == tag).all() and time.monotonic() < deadline:
-                time.sleep(5e-5)
-            if not (tags == tag).all():
-                self._stream.synchronize()
-                if not (tags == tag).all():
-                    bad = int(np.nonzero(tags != tag)[0][0])
-                    raise hip.HipError('frame %r never published its result block (tag reads %r): '
-                                       'the frame graph did not run to the decode kernel' % (tag, float(tags[bad])))
+        out = self._out_np
+        wait_tags(out[:, 8], self._tag[0], self._stream, self.e.opt['spin_seconds'])
         res = {b: out[b, :8].copy() for b in self._items}
         self.book.stepped(res)
         return res
@@ -2605,8 +2605,7 @@ class BatchSession:
         """Memory feature i of `slot` as an NCHW-shaped view [1,256,7,7] of its bank row."""
         if self.book.pending[slot] and i == self.book.n[slot] - 1:
             self.flush()
-        r = self.book.row(slot, 2 + i)
-        return self.bank[r:r + 1].permute(0, 3, 1, 2)
+        return self.mem.view(self.book.row(slot, 2 + i))
 
 
 class SlotMemory(object):

@@ -97,17 +97,8 @@ class MultiVideoTracker(object):
         res = {}
         for key in frames:
             state, bs, slot = self._videos[key]
-            out = outs[id(bs)][slot]
-            p = state['p']
             scale_z, tsz = pre[key]
-            pos, sz = USOTTracker._apply_box(p, out[3:7], out[2], out[1], state['target_pos'], tsz, scale_z)
-            score = np.float32(out[1])
-            state['memory_confidences'].append(score)
-            pos[0] = max(0, min(state['im_w'], pos[0]))
-            pos[1] = max(0, min(state['im_h'], pos[1]))
-            sz[0] = max(10, min(state['im_w'], sz[0]))
-            sz[1] = max(10, min(state['im_h'], sz[1]))
-            state.update(target_pos=pos, target_sz=sz, cls_score=score, p=p)
+            USOTTracker._apply_result(state, outs[id(bs)][slot], tsz, scale_z)
             res[key] = state
         return res
 

@@ -253,6 +253,23 @@ class USOTTracker(object):
         state['_conf_n'] = n
         return buf[:n]
 
+    @staticmethod
+    def _commit(state, pos, sz, score):
+        """usot_tracker.py:265-276: the frame's confidence joins the memory's, position and size are clamped to the image."""
+        state['memory_confidences'].append(score)
+        pos[0] = max(0, min(state['im_w'], pos[0]))
+        pos[1] = max(0, min(state['im_h'], pos[1]))
+        sz[0] = max(10, min(state['im_w'], sz[0]))
+        sz[1] = max(10, min(state['im_h'], sz[1]))
+        state.update(target_pos=pos, target_sz=sz, cls_score=score, p=state['p'])
+
+    @staticmethod
+    def _apply_result(state, out, tsz_scaled, scale_z):
+        """A frame graph's result block (Session.collect's layout) applied to the state it was submitted from.  The graph has
+        already appended the pooled feature to the session's bank, which state['memory_features'] views (usot_tracker.py:264)."""
+        pos, sz = USOTTracker._apply_box(state['p'], out[3:7], out[2], out[1], state['target_pos'], tsz_scaled, scale_z)
+        USOTTracker._commit(state, pos, sz, np.float32(out[1]))
+
     def track(self, state, im):
         """usot_tracker.py:202-276."""
         p, net = state['p'], state['net']
@@ -274,10 +291,7 @@ class USOTTracker(object):
                 own = (x_crop.is_cuda and x_crop.device == sess.e.device and x_crop.dtype == torch.float32
                        and x_crop.is_contiguous() and x_crop.numel() == sess.x.numel())
                 out = sess.frame(x_crop, picks, target_sz * scale_z, inplace=own)
-            pos, sz = self._apply_box(p, out[3:7], out[2], out[1], target_pos, target_sz * scale_z, scale_z)
-            score = np.float32(out[1])
-            # the frame graph has already appended the pooled feature to the session's bank, which
-            # state['memory_features'] views (usot_tracker.py:264)
+            self._apply_result(state, out, target_sz * scale_z, scale_z)
         else:
             dev = _dev_of(net)
             feats = state['memory_features']
@@ -286,11 +300,5 @@ class USOTTracker(object):
             pos, sz, score, feat = self.update(net, x_crop.unsqueeze(0).to(dev), target_pos, target_sz * scale_z,
                                                state['window'], scale_z, p, template_mem=mem, score_mem=score_mem)
             state['memory_features'].append(feat)
-        state['memory_confidences'].append(score)
-
-        pos[0] = max(0, min(state['im_w'], pos[0]))
-        pos[1] = max(0, min(state['im_h'], pos[1]))
-        sz[0] = max(10, min(state['im_w'], sz[0]))
-        sz[1] = max(10, min(state['im_h'], sz[1]))
-        state.update(target_pos=pos, target_sz=sz, cls_score=score, p=p)
+            self._commit(state, pos, sz, score)
         return state
