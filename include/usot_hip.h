@@ -318,7 +318,8 @@ int usot_plan_add_pw_kstream(void *plan, const void *x, const void *w, const flo
  * output pixel and fetches its MFMA B fragments straight from global memory three k-chunks ahead, W streams through LDS.
  * x, y NHWC dense, w [Cout][9 Cin] (k = (kh*3 + kw)*Cin + ci) in the storage type (dtype 0 = bf16, 1 = fp16), bias fp32 or
  * NULL, stride 1 | 2, pad <= dil, act USOT_ACT_NONE | USOT_ACT_RELU.  Shapes: usot_conv_kstream_supported (Cin 256 | 512,
- * Cout a multiple of 256, 3 x 3). */
+ * Cout a multiple of 256, 3 x 3).  The batch must hold MORE than dil * (W + 1) pixels (N * H * W; USOT_EINVAL otherwise, for
+ * a plan when the op runs): a lane parks a tap outside the image at most that far from the start of x. */
 int usot_conv_kstream_lp(void *stream, const void *x, const void *w, const float *bias, void *y,
                          int N, int H, int W, int Cin, int Cout, int stride, int pad, int dil, int act, int dtype);
 int usot_conv_kstream_supported(int Cin, int Cout, int KH, int KW);

@@ -247,7 +247,7 @@ extern "C" int usot_conv_kstream_supported(int Cin, int Cout, int KH, int KW)
 }
 
 /* y = act(conv3x3(x, w) + bias): NHWC dense, x / w / y in the storage type (dtype 0 = bf16, 1 = fp16), w [Cout][9 Cin] with
- * k = (kh*3 + kw)*Cin + ci, bias fp32 or NULL; stride 1 | 2, any pad / dilation; act USOT_ACT_NONE | USOT_ACT_RELU.
+ * k = (kh*3 + kw)*Cin + ci, bias fp32 or NULL; stride 1 | 2, 0 <= pad <= dil, N * H * W > dil * (W + 1) pixels; act USOT_ACT_NONE | USOT_ACT_RELU.
  * Shapes: usot_conv_kstream_supported(Cin, Cout, 3, 3) (Cin 256 | 512, Cout a multiple of 256). */
 extern "C" int usot_conv_kstream_lp(void *stream, const void *x, const void *w, const float *bias, void *y,
                                     int N, int H, int W, int Cin, int Cout, int stride, int pad, int dil, int act, int dtype)
@@ -262,6 +262,9 @@ extern "C" int usot_conv_kstream_lp(void *stream, const void *x, const void *w, 
     if (p.OH <= 0 || p.OW <= 0) return USOT_EINVAL;
     // the centre tap of every output pixel lies inside the image (the kernel parks out-of-image taps there), offsets fit 32 bits
     if ((p.OH - 1) * stride - pad + dil >= H || (p.OW - 1) * stride - pad + dil >= W || (long)N * H * W * Cin * 2 >= 0xffffffffL) return USOT_EINVAL;
+    // a lane whose tap falls outside the image and whose centre pixel lies before the tap's offset from it reads AT that offset
+    // (set_tap: park <= 0), at most dil * (W + 1) pixels from the start of x: that pixel must exist
+    if ((long)N * H * W <= (long)dil * (W + 1)) return USOT_EINVAL;
     const long M = (long)N * p.OH * p.OW;
     if (M > 0x7fffffffL) return USOT_EINVAL;
     p.M = (int)M; p.npanels = (int)((M + CK_BM - 1) / CK_BM); p.NT = Cout / CK_BN;
