@@ -570,6 +570,70 @@ int     usot_box_exp_fwd_f32(void *stream, const usot_box_exp_desc *d);         
 int     usot_box_exp_bwd_f32(void *stream, const usot_box_exp_desc *d);          /* dp, dadjust, dbias: the ones that are non-NULL */
 int64_t usot_box_exp_ws_floats(const usot_box_exp_desc *d);                      /* host only: 5 * ceil(R / 256) */
 
+/* ---- fused SGD step over every tensor of an optimiser in ONE launch (csrc/sgd.hip; the reference's scripts/train_usot.py:
+ * SGD with momentum 0.9 and weight decay 1e-4 over three parameter groups, behind `if is_valid_number(loss.item())`).
+ * All values are fp32; per element of a tensor, with the tensor's own lr, weight_decay, momentum, grad_scale and flags:
+ *   g'   = maximize ? -g : g
+ *   d    = g' + weight_decay * p
+ *   buf' = first ? d : momentum * buf + grad_scale * d      (momentum != 0; grad_scale = 1 - dampening)
+ *   step = momentum == 0 ? d : nesterov ? d + momentum * buf' : buf'
+ *   p'   = p - lr * step
+ * The compiler may fuse multiply-adds.  The host forms 1 - dampening in double and rounds it to fp32 once.  With `first` set
+ * buf is not read; with momentum == 0 buf is neither read nor written and may be NULL.  One pass: p, g and buf read, p and buf
+ * written - 20 bytes per element (24 with zero_grads).
+ *
+ * The kernel reads a DEVICE-resident table: T records of usot_sgd_tensor followed by a chunk list of n_chunks entries
+ * {int32 tensor, int32 chunk_in_tensor}; a chunk is usot_sgd_chunk_elems() consecutive elements of one tensor (a compile-time
+ * multiple of 4 floats), the last chunk of a tensor is short, and a tensor with n == 0 has no chunk.  One workgroup handles one
+ * chunk and strides over the chunk list by the grid, which is min(n_chunks, usot_sgd_grid_cap()) workgroups.  A tensor whose p, g
+ * and buf (where it has one) are all 16-byte aligned is moved with 16-byte loads and stores and a scalar n % 4 tail; any other
+ * tensor takes the scalar path as a whole.  The choice is per tensor, so it is uniform over a workgroup.
+ *
+ * usot_sgd_table_bytes and usot_sgd_table_fill are host functions and touch no device: the first sizes the table image for
+ * the element counts n[0 .. T) and leaves the chunk count in *n_chunks (which may be NULL), the second validates the records
+ * and writes the image into HOST memory - the caller uploads it.  usot_sgd_table_bytes answers USOT_EINVAL for a NULL n, T < 1,
+ * a negative n[i] or more than 2^31 - 1 chunks.  usot_sgd_table_fill answers USOT_EINVAL, with the image untouched, for: t or
+ * image NULL, T < 1; p or g NULL; buf NULL with momentum != 0; a pointer that is not 4-byte aligned; n < 0; a non-finite or
+ * negative lr, weight_decay or momentum; a non-finite grad_scale; nesterov with momentum == 0 or grad_scale != 1; flag bits
+ * other than the three below; `bytes` below usot_sgd_table_bytes.  `reserved` is written as 0 whatever it held: equal records
+ * give equal images, byte for byte.
+ *
+ * usot_sgd_step_f32 launches once (not at all for n_chunks == 0, which is USOT_OK).  USOT_EINVAL before the device is touched:
+ * d or table NULL, a table that is not 8-byte aligned, a guard or counters that is not 4-byte aligned, T < 1, n_chunks < 0 or
+ * above 2^31 - 1.  T and n_chunks must be the ones
+ * the uploaded image was made with.
+ *   guard     NULL, or one float in device memory (the loss) that every workgroup reads.  When it is NaN, +-Inf or > 1e4 the
+ *             launch writes no p and no buf: the reference's is_valid_number, so 1e4 itself and -1e30 are valid.
+ *   counters  NULL, or two int32 in device memory: one thread of workgroup 0 adds 1 to counters[0] (step applied) or
+ *             counters[1] (step skipped) with a plain load and store - launches are stream-ordered, no atomic.
+ *   zero_grads != 0: every g the launch covers is overwritten with 0, whether the step was applied or skipped.
+ * A launch writes p, buf (applied steps), g (zero_grads) and one counter, and nothing else; the table and the guard are only read. */
+#define USOT_SGD_FIRST     1   /* flags bit 0: buf' = d (the tensor's first step; buf is not read) */
+#define USOT_SGD_NESTEROV  2   /* flags bit 1 */
+#define USOT_SGD_MAXIMIZE  4   /* flags bit 2 */
+typedef struct usot_sgd_tensor {
+    float *p;                       /* [n] parameter, updated in place */
+    float *g;                       /* [n] gradient; zeroed with zero_grads, otherwise only read */
+    float *buf;                     /* [n] momentum buffer, updated in place; NULL allowed with momentum == 0 */
+    int64_t n;                      /* elements; 0 = the tensor takes no part */
+    float lr, weight_decay, momentum, grad_scale;
+    int32_t flags;                  /* USOT_SGD_* */
+    int32_t reserved;               /* 0 in the image: three pointers, n, four floats and flags are 52 bytes, the record is 56 */
+} usot_sgd_tensor;
+typedef struct usot_sgd_launch {
+    const void *table;              /* device address of the uploaded image */
+    const float *guard;             /* device; NULL = no guard */
+    int32_t *counters;              /* device, 2 x int32; NULL = not counted */
+    int64_t n_chunks;               /* of the image (usot_sgd_table_bytes) */
+    int32_t T;                      /* records in the image */
+    int32_t zero_grads;
+} usot_sgd_launch;
+int     usot_sgd_chunk_elems(void);                                               /* host only: elements per chunk */
+int     usot_sgd_grid_cap(void);                                                  /* host only: most workgroups of a launch */
+int64_t usot_sgd_table_bytes(const int64_t *n, int T, int64_t *n_chunks);        /* host only */
+int     usot_sgd_table_fill(const usot_sgd_tensor *t, int T, void *image, int64_t bytes);      /* host only */
+int     usot_sgd_step_f32(void *stream, const usot_sgd_launch *d);
+
 /* ---- fused GroupDW on NHWC (connect.py:86-102): three depthwise xcorrs and the
  * softmax(weight)-weighted sum in one pass, no intermediate maps.
  *   branch b: x_b NHWC [XS][OH+hk_b-1][OW+wk_b-1] (pixel stride x_cs, channel offset x_co)

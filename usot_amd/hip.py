@@ -6,6 +6,7 @@ raises.  torch is used only for device memory and the current HIP stream.
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -100,6 +101,22 @@ class BoxExpDesc(C.Structure):
     _fields_ = [('p', C.c_void_p), ('adjust', C.c_void_p), ('bias', C.c_void_p), ('y', C.c_void_p), ('dy', C.c_void_p),
                 ('dp', C.c_void_p), ('dadjust', C.c_void_p), ('dbias', C.c_void_p), ('ws', C.c_void_p),
                 ('R', C.c_int32), ('C', C.c_int32)]
+
+
+SGD_FIRST, SGD_NESTEROV, SGD_MAXIMIZE = 1, 2, 4       # usot_sgd_tensor.flags
+
+
+class SgdTensor(C.Structure):
+    """usot_sgd_tensor"""
+    _fields_ = [('p', C.c_void_p), ('g', C.c_void_p), ('buf', C.c_void_p), ('n', C.c_int64),
+                ('lr', C.c_float), ('weight_decay', C.c_float), ('momentum', C.c_float), ('grad_scale', C.c_float),
+                ('flags', C.c_int32), ('reserved', C.c_int32)]
+
+
+class SgdLaunch(C.Structure):
+    """usot_sgd_launch"""
+    _fields_ = [('table', C.c_void_p), ('guard', C.c_void_p), ('counters', C.c_void_p), ('n_chunks', C.c_int64),
+                ('T', C.c_int32), ('zero_grads', C.c_int32)]
 
 
 class GroupDWDesc(C.Structure):
@@ -262,6 +279,12 @@ def lib():
         for name in ('usot_batchnorm_add_fwd_f32', 'usot_batchnorm_add_bwd_f32'):
             getattr(L, name).argtypes = [C.c_void_p, C.c_void_p]
         L.usot_box_exp_ws_floats.restype = C.c_int64
+        # the fused SGD step (csrc/sgd.hip): bound like the head's operators, not listed in EXPORTS
+        L.usot_sgd_chunk_elems.argtypes = L.usot_sgd_grid_cap.argtypes = []
+        L.usot_sgd_table_bytes.argtypes = [C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int64)]
+        L.usot_sgd_table_bytes.restype = C.c_int64
+        L.usot_sgd_table_fill.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int64]
+        L.usot_sgd_step_f32.argtypes = [C.c_void_p, C.c_void_p]
         L.PrRoIPoolingForwardGpu.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_float, C.c_int]
         L.PrRoIPoolingForwardGpu.restype = None
         L.usot_prroi_pool_backward_f32.argtypes = [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_float]
@@ -973,6 +996,53 @@ def box_exp_backward(dy, p, adjust, bias, need=(True, True, True)):
     d.dp, d.dadjust, d.dbias, d.ws = ptr(dp), ptr(da), ptr(db), ptr(ws)
     check(lib().usot_box_exp_bwd_f32(stream(), C.byref(d)), 'usot_box_exp_bwd_f32')
     return dp, da, db
+
+
+def sgd_chunk_elems():
+    """elements of one chunk of the fused SGD step (host only)"""
+    return int(lib().usot_sgd_chunk_elems())
+
+
+def sgd_grid_cap():
+    """most workgroups of one launch of the fused SGD step (host only)"""
+    return int(lib().usot_sgd_grid_cap())
+
+
+def sgd_table(records):
+    """Table image of the fused SGD step for `records` (a ctypes array of SgdTensor, or a sequence of them): validated and laid out
+    by usot_sgd_table_fill in HOST memory -> (image as a ctypes array of bytes, n_chunks).  Touches no device; the caller uploads
+    the image and hands its device copy to sgd_step with the same T and n_chunks."""
+    if not isinstance(records, C.Array):
+        records = (SgdTensor * len(records))(*records)
+    T = len(records)
+    if T < 1 or records._type_ is not SgdTensor:
+        raise HipError('sgd_table: at least one SgdTensor record expected')
+    words = C.sizeof(SgdTensor) // 8                     # the records as int64 words: n is word 3 of each
+    n = np.ascontiguousarray(np.frombuffer(records, dtype=np.int64)[SgdTensor.n.offset // 8::words])
+    chunks = C.c_int64(0)
+    nbytes = lib().usot_sgd_table_bytes(n.ctypes.data_as(C.POINTER(C.c_int64)), T, C.byref(chunks))
+    if nbytes < 0:
+        check(int(nbytes), 'usot_sgd_table_bytes')
+    image = (C.c_ubyte * nbytes)()
+    check(lib().usot_sgd_table_fill(records, T, image, nbytes), 'usot_sgd_table_fill')
+    return image, int(chunks.value)
+
+
+def sgd_step(table, T, n_chunks, guard=None, counters=None, zero_grads=False):
+    """One launch of the fused SGD step over the uploaded table image `table` (uint8 device tensor; T records, n_chunks chunks -
+    sgd_table).  guard: 1-element fp32 device tensor (the loss) or None; counters: int32 device tensor [2] (applied, skipped) or
+    None; zero_grads: store 0 over every gradient the launch covers."""
+    _dev(table, torch.uint8)
+    if guard is not None and _dev(guard).numel() != 1:
+        raise HipError('sgd_step: the guard holds %d values, not one' % guard.numel())
+    if counters is not None and (_dev(counters, torch.int32).numel() != 2 or not counters.is_contiguous()):
+        raise HipError('sgd_step: counters of shape %s are not two dense int32' % (tuple(counters.shape),))
+    if not table.is_contiguous() or table.numel() < T * C.sizeof(SgdTensor) + 8 * n_chunks:
+        raise HipError('sgd_step: a table of %d bytes does not hold %d records and %d chunks' % (table.numel(), T, n_chunks))
+    d = SgdLaunch()
+    d.table, d.guard, d.counters = table.data_ptr(), ptr(guard), ptr(counters)
+    d.n_chunks, d.T, d.zero_grads = int(n_chunks), int(T), int(bool(zero_grads))
+    check(lib().usot_sgd_step_f32(stream(), C.byref(d)), 'usot_sgd_step_f32')
 
 
 def groupdw_desc(xs, zs, out, wsm, *, S, x_rep, OH, OW, Cc, x_cs, x_co, z_cs, z_co, cols=0):
